@@ -1,24 +1,27 @@
 #!/usr/bin/env python3
 """bench.py — env-steps/sec of the ARCLE hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config c3|c2|c4|c5]
+    python bench.py --gpus N --steps K --warmup W [--config c3|c2|c4|c5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 (`python bench.py --gpus N` without a launcher spawns the N ranks itself.)
 
 A "step" is ONE pass of the hot path over one batch: a single launch of the step kernel that applies one (selection,
 operation) action to every env of this GPU.  Tasks, state and the whole action stream are resident in HBM before the
-timed region starts.  HEADLINE (`value`, `ms_per_step`, `roofline`) = the step()-per-call form: a region's K launches are K
+timed region starts.  HEADLINE (`value`, `ms_per_step`) = the step()-per-call form: the region's K launches are K
 `arcle_step_bbox` calls, none of which sees the next step's actions (the loop a(t+1) = policy(obs(t)) of the reference's
 examples/example_bbox.py:13-15).  Since round 5 every such launch orders ITSELF (object operations to the waves that start first,
-derived inside groups of 32 envs from the operations the launch is about to execute; scheduling only).  c3 times beside the headline —
-same run, same event clock, top-level `forms` block — the same K launches enqueued by ONE `arcle_step_many` call (what
-`ARCVecEnv.capture` records) and the K single-step calls with the dispatch order switched off (the plain instantiation: every wave steps
-the env of its own slot) — the in-run A/B of the ordering (`--no-forms` skips that
-leg).  Envs are independent, so N GPUs = N shards, no data-path collective (weak scaling).
-OUTPUT: rank 0 prints ONE compact JSON line on stdout (< 3 KB, the LAST line; the contract fields + `forms`, `roofline`,
-`cpu_baseline`, `sustained`, `legs_us_per_step`, `collective` for N > 1); the full record (every leg with its own roofline block,
-per-region times) goes to stderr as one `BENCH_FULL {...}` line and to gpurun_out/bench_full_<config>_n<N>_k<K>.json.
+derived inside groups of 32 envs from the operations the launch is about to execute; scheduling only).
+A plain run does only what the headline needs: set-up, clock ramp, W warm-up steps, the timed K steps, the outputs of the last step when
+`--dump-outputs DIR` is given (DIR/<name>.npy, float32 / float64, < 64 MB: see dump_outputs) and the result line.
+`--full` adds everything else, after the headline and outside its clock: the `roofline` block, for c3 the `forms` block — same run,
+same event clock — the same K launches enqueued by ONE `arcle_step_many` call (what `ARCVecEnv.capture` records) and the K
+single-step calls with the dispatch order switched off (the plain instantiation: every wave steps the env of its own slot), the in-run
+A/B of the ordering (`--no-forms` skips it) —, the `extras` legs, `cpu_baseline` and `sustained` (N = 1, c3), `multi` (N > 1, c3) and
+`floodfill` (c5).  Envs are independent, so N GPUs = N shards, no data-path collective (weak scaling).
+OUTPUT: rank 0 prints ONE compact JSON line on stdout (< 3 KB, the LAST line; the contract fields, `collective` for N > 1, and with
+--full `forms`, `roofline`, `cpu_baseline`, `sustained`, `legs_us_per_step`); the full record (every leg with its own roofline block,
+per-region times) goes to stderr as one `BENCH_FULL {...}` line.
 Workloads (`config.workload` names the one that ran):
   c3 (default, the headline: BASELINE configs[2])  O2ARCv2Env 30x30, 8192 envs/GPU, 35 ops uniform, BBox 5-tuples
       uniform, on-device auto-reset of terminated envs
@@ -27,12 +30,14 @@ Workloads (`config.workload` names the one that ran):
       all_gather_into_tensor over RCCL (BASELINE configs[3])
   c5  ARCEnv 27-op table 30x30, 4096 envs/GPU, 70 % FloodFill point seeds on large-region grids (BASELINE configs[4])
 
-Timing: after an untimed clock ramp and W warm-up steps, the region "barrier + synchronize, exactly K steps, synchronize
-+ barrier" is run R times (R reported as `timing.regions`); `value`/`ms_per_step` are the MEDIAN region (max over
-ranks per region).  A region that is one hipGraph replay is clocked by HIP events recorded on the launch stream between the two
-synchronisations (device time of exactly the K steps; the host-clock figure of the same regions is `timing.host_region_ms`);
-eagerly launched regions are clocked by the host.  (The K launches are captured once: every region replays the same K action
-batches on an evolving state.)  Besides the contract fields the line carries
+Timing: after an untimed clock ramp (on the reset state, reset again afterwards) and W warm-up steps, the region
+"barrier + synchronize, exactly K steps, synchronize + barrier" is run once — `--regions R` runs it R times (R reported as
+`timing.regions`, R x K steps timed); `value`/`ms_per_step` are the MEDIAN region (max over ranks per region) divided by K.  The K
+launches are captured as hipGraphs of at most GRAPH_STEPS launches each (one graph for K <= GRAPH_STEPS; a longer region replays the
+graph of the first GRAPH_STEPS action batches back to back and a graph of the remainder, all between the same two events).  A region of
+hipGraph replays is clocked by HIP events recorded on the launch stream between the two synchronisations (device time of exactly the
+K steps; the host-clock figure of the same regions is `timing.host_region_ms`); eagerly launched regions are clocked by the host.
+(Every region replays the same action batches on an evolving state.)  With --full the line also carries
   roofline      of the step kernel, all bytes counted BY THE KERNEL in this run (accounting instantiation, region 0 replayed once,
                 untimed): `achieved` / `frac` = algorithmic HBM bytes (planes semantically read + written by the
                 executed op / mode + 56 B) / the average launch duration (HIP-event pair on the launch stream around the K
@@ -50,7 +55,7 @@ batches on an evolving state.)  Besides the contract fields the line carries
                 ALL host cores) and `numpy_step` = a plain-NumPy one-env-at-a-time step() loop with the reference's call
                 structure (oracle/numpy_env.py; leaner than the reference itself, labelled so), 1 process / all cores;
   sustained     (N=1) the headline graph replayed back to back on a side thread for the ~15 s of the single-threaded CPU legs;
-  collective    (N>1) backend, world size and the number of ranks an all-reduce of ones actually counted;
+  collective    (N>1, also without --full) backend, world size and the number of ranks an all-reduce of ones actually counted;
   multi         (N>1, c3) bounded legs of BASELINE configs[3] / [4] on the same process group, after the headline: c4 = 8192 envs/GPU,
                 step + ONE packed all-gather per step (overlapped on a side stream / serial / the collective alone, GB/s), c5 = ARCEnv
                 4096 envs/GPU FloodFill-heavy, sharded without a collective (multi_legs below; --no-multi skips them).
@@ -75,6 +80,8 @@ HBM_PEAK = 8.0e12  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH
 STEP_AUTORESET = 1
 STEP_PACK_OBS = 256
 STEP_ROWS_INCREMENTAL = 512
+GRAPH_STEPS = 400  # step launches per captured hipGraph = the default --steps: a longer region replays the default run's graph back to back
+DUMP_ENVS, DUMP_PLANE_ENVS, DUMP_LIMIT = 8192, 1024, 64 << 20  # --dump-outputs: envs written, envs of the planes besides `grid`, bytes
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -184,6 +191,16 @@ def frontier_rounds_sample(grids, seeds, limit=64):
             f, r = grow, r + 1
         out.append(r)
     return {"sample": len(out), "mean": float(np.mean(out)), "p90": float(np.percentile(out, 90)), "max": int(np.max(out))}
+
+
+def staged_batches(K, Wm, action_batches=0):
+    """Distinct action batches staged in HBM for --steps K --warmup Wm: 5 to 50 graphs' worth, as far as 2048 batches, at least one
+    graph + the warm-up (its share capped at GRAPH_STEPS).  Warm-up step i reads batch i % S, step t of a region batch (Wm + t % C) % S
+    with C = min(K, GRAPH_STEPS): every region, and every GRAPH_STEPS launches of a longer one, repeat the same batches."""
+    C, Ws = min(K, GRAPH_STEPS), min(Wm, GRAPH_STEPS)
+    if action_batches:
+        return max(C + Ws, action_batches)
+    return min(C * max(5, min(50, math.ceil(2000 / C))) + Ws, max(C + Ws, 2048))
 
 
 CONFIGS = {
@@ -348,18 +365,39 @@ def _r(x, nd=4):
     return x
 
 
-def emit(out, a):
+def dump_outputs(path, batch):
+    """--dump-outputs: what the timed path hands its caller after the LAST timed step, one float32 .npy per array under `path` — the
+    step's outputs (`reward`, `terminated`), the state it leaves (`grid` and the other state planes as [envs, H, W], every field of the
+    per-env record as `rec_<field>`) and the per-env step counters (`counters`, float64).  Up to DUMP_ENVS envs are written whole;
+    beyond that a fixed seeded sample (`env_index`), and the planes besides `grid` (and the inputs `input` / `answer`, left out) for a
+    fixed sample of DUMP_PLANE_ENVS of those (`plane_env_index`): at most ~56 MB whatever the batch size.  Same arguments, same files."""
+    from arcle_amd.engine import REC_FIELDS
+    n = batch.N
+    idx = np.arange(n) if n <= DUMP_ENVS else np.sort(np.random.default_rng(0).choice(n, DUMP_ENVS, replace=False))
+    pidx = idx if len(idx) <= DUMP_PLANE_ENVS else np.sort(np.random.default_rng(1).choice(idx, DUMP_PLANE_ENVS, replace=False))
+    ti, tp = torch.as_tensor(idx, device=batch.device), torch.as_tensor(pidx, device=batch.device)
+    arrays = {"env_index": idx.astype(np.float64), "plane_env_index": pidx.astype(np.float64),
+              "reward": batch.reward[ti], "terminated": batch.term[ti], "counters": batch.cnt[ti].double()}
+    for k in batch.planes:
+        if k not in ("input", "answer"):
+            arrays[k] = batch.plane(k)[ti if k == "grid" else tp]
+    for k in REC_FIELDS:
+        arrays["rec_" + k] = batch.field(k)[ti]
+    arrays = {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs would write {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return total
+
+
+def emit(out):
     """stdout gets ONE compact JSON line (< 3 KB: the driver keeps an 8 KB tail and parses the last line); the full record — every
-    leg with its own roofline block, the per-region times — goes to stderr as one `BENCH_FULL ` line and, when the directory is
-    writable, to gpurun_out/bench_full.json."""
+    leg with its own roofline block, the per-region times — goes to stderr as one `BENCH_FULL ` line."""
     full = json.dumps(out)
     print("BENCH_FULL " + full, file=sys.stderr, flush=True)
-    try:
-        os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-        with open(os.path.join(ROOT, "gpurun_out", f"bench_full_{a.config}_n{out['n_gpus']}_k{out['steps']}.json"), "w") as f:
-            f.write(full + "\n")
-    except OSError:
-        pass
     c = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                              "vs_baseline", "dtype", "data")}
     c["value"], c["ms_per_step"] = _r(out["value"], 6), _r(out["ms_per_step"], 6)
@@ -430,7 +468,7 @@ def emit(out, a):
             "gather_GBps": _r(m["c4"]["gather_GBps"]), "gather_GBps_per_link_dir": _r(m["c4"]["gather_GBps_per_link_dir"]),
             "c5_us_per_step": _r(m["c5"]["us_per_step"]), "c5_value": _r(m["c5"]["value"], 6), "c5_global_envs": m["c5"]["global_envs"],
             "transport": m["c4"]["transport"][:40], "steps_per_region": m["steps_per_region"], "regions": m["regions"]}
-    c["full_record"] = "stderr line BENCH_FULL / gpurun_out/bench_full_*.json"
+    c["full_record"] = "stderr line BENCH_FULL"
     line = json.dumps(c)
     if len(line) > 3800:  # never let the headline grow past what the driver keeps
         for k in ("legs_us_per_step", "sustained", "floodfill"):
@@ -1149,13 +1187,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=40)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c3")
     ap.add_argument("--envs-per-gpu", type=int, default=0, help="override the config's batch size (kernel sweeps)")
-    ap.add_argument("--regions", type=int, default=0, help="timed regions of K steps (default: 5, more for small K)")
+    ap.add_argument("--regions", type=int, default=0, help="timed regions of K steps (default: 1; `value` = the median region)")
     ap.add_argument("--action-batches", type=int, default=0, help="distinct action batches staged in HBM (default: up to 2048, the regions cycle "
                     "through them; a small number keeps the action stream cache-resident — a policy that writes one batch per step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the non-headline legs (kernel A/B runs)")
-    ap.add_argument("--no-multi", action="store_true", help="N > 1: skip the bounded c4 (step + RCCL all-gather) and c5 (sharded FloodFill) legs after the c3 headline")
-    ap.add_argument("--no-forms", "--no-ordered", dest="no_ordered", action="store_true", help="skip the `forms` leg (the region's K launches as ONE arcle_step_many call, "
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (step outputs and "
+                    "the state it leaves) as DIR/<name>.npy, float32 / float64, at most 64 MB")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run everything else: roofline (kernel-counted bytes), forms, "
+                    "extras, cpu_baseline + sustained, multi (N > 1), floodfill (c5)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the non-headline legs (kernel A/B runs)")
+    ap.add_argument("--no-multi", action="store_true", help="--full, N > 1: skip the bounded c4 (step + RCCL all-gather) and c5 (sharded FloodFill) legs after the c3 headline")
+    ap.add_argument("--no-forms", "--no-ordered", dest="no_ordered", action="store_true", help="--full: skip the `forms` leg (the region's K launches as ONE arcle_step_many call, "
                     "and the K single-step calls with the dispatch order off)")
     ap.add_argument("--no-graph", action="store_true", help="launch the K steps of a region eagerly instead of as one hipGraph")
     ap.add_argument("--no-ramp", action="store_true", help="skip the untimed clock-ramp launches (counter-collection runs)")
@@ -1196,12 +1238,11 @@ def main():
     H, W, kind = cfg["H"], cfg["W"], cfg["kind"]
     n = a.envs_per_gpu or cfg["envs"]
     K, Wm = a.steps, a.warmup
-    R = a.regions or max(5, min(50, math.ceil(2000 / max(K, 1))))
-    if shared_gpu and a.config == "c4" and not a.regions:
-        R = 3  # (ranks sharing one GPU gather through a CPU bounce, ~0.2 s per step: a functional leg, not a measurement)
-    S = min(K * R + Wm, max(K + Wm, 2048))  # distinct action batches staged in HBM (regions cycle through them)
-    if a.action_batches:
-        S = max(K + Wm, a.action_batches)
+    if K < 1 or Wm < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    R = a.regions or 1
+    C = min(K, GRAPH_STEPS)  # launches per captured graph
+    S = staged_batches(K, Wm, a.action_batches)
 
     # shard = contiguous global env ids [rank*n, (rank+1)*n); per-shard seeds keyed by rank
     batch = EnvBatch(n, H, W, cfg["max_trial"], kind, dev)
@@ -1281,40 +1322,38 @@ def main():
             pass
         torch.cuda.synchronize(dev)
 
-    # ---- untimed: W warm-up steps ---------------------------------------------------------------------------------
-    for i in range(Wm):
-        step(i)
-    join_side()
-    torch.cuda.synchronize(dev)
-    # snapshot of the state region 0 starts from (replayed below for the byte accounting)
-    snap = {k: v.clone() for k, v in batch.planes.items()}
-    snap_rec, snap_cnt = batch.rec.clone(), batch.cnt.clone()
-
-    # The K steps of a region are captured once into a hipGraph (K launches of arcle_step_kernel, each with its own action batch)
-    # and replayed per region: a launch-bound inner loop belongs in a graph, and the host then issues one call per region instead
-    # of K.  (With more than one rank c4 keeps eager launches when ranks share a GPU: its collective goes through the host.)
+    # The K steps of a region are captured once into hipGraphs (K launches of arcle_step_kernel, each with its own action batch: one graph
+    # of K launches up to GRAPH_STEPS, else a graph of the first GRAPH_STEPS replayed K // GRAPH_STEPS times + one of the remainder) and
+    # replayed per region: a launch-bound inner loop belongs in a graph, and the host then issues one call per graph instead of one per
+    # launch.  (With more than one rank c4 keeps eager launches when ranks share a GPU: its collective goes through the host.)
     # HEADLINE = the step()-per-call form: K arcle_step_bbox calls, none of which knows the next step's actions (the loop
-    # a(t+1) = policy(obs(t)) of examples/example_bbox.py:13-15); every launch orders itself.  c3 also times, beside it
-    # and with the same clock, the same K launches enqueued by ONE arcle_step_many call (what ARCVecEnv.capture records) and the K
-    # single-step calls with the dispatch order off (the plain instantiation) -> the top-level `forms` block.
-    graph = None
+    # a(t+1) = policy(obs(t)) of examples/example_bbox.py:13-15); every launch orders itself.  With --full c3 also times,
+    # beside it and with the same clock, the same K launches enqueued by ONE arcle_step_many call (what ARCVecEnv.capture records) and the
+    # K single-step calls with the dispatch order off (the plain instantiation) -> the top-level `forms` block (K <= GRAPH_STEPS).
+    graph = graph_tail = None
     graph_many = graph_plain = None
-    many = a.config == "c3" and gather is None and not a.no_ordered and K > 1
+    many = a.full and a.config == "c3" and gather is None and not a.no_ordered and 1 < K <= GRAPH_STEPS
     many_out = (torch.empty((K, n), dtype=torch.int32, device=dev), torch.empty((K, n), dtype=torch.uint8, device=dev)) if many else None
     if not a.no_graph and not (gather is not None and shared_gpu):
         try:
-            graph = torch.cuda.CUDAGraph()
             cap = torch.cuda.Stream(dev)
             cap.wait_stream(stream)
-            if gather is not None:
-                done[0] = done[1] = None
-            with torch.cuda.graph(graph, stream=cap):
-                cs = torch.cuda.current_stream(dev)
-                for i in range(Wm, Wm + K):  # (c4 with a process group: the RCCL collectives are captured as well, on the forked side stream)
-                    step(i, cs.cuda_stream, cs)
-                join_side(cs)
-            if gather is not None:
-                done[0] = done[1] = None
+
+            def capture(steps):
+                g = torch.cuda.CUDAGraph()
+                if gather is not None:
+                    done[0] = done[1] = None
+                with torch.cuda.graph(g, stream=cap):
+                    cs = torch.cuda.current_stream(dev)
+                    for i in range(Wm, Wm + steps):  # (c4 with a process group: the RCCL collectives are captured as well, on the forked side stream)
+                        step(i, cs.cuda_stream, cs)
+                    join_side(cs)
+                if gather is not None:
+                    done[0] = done[1] = None
+                return g
+            graph = capture(C)
+            if K % C:
+                graph_tail = capture(K % C)
             if many:
                 graph_many = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph_many, stream=cap):
@@ -1329,38 +1368,46 @@ def main():
                 batch.set_dispatch_order(True)
         except Exception as exc:  # capture unsupported: eager launches
             print(f"bench: hipGraph capture failed ({exc}); eager launches", file=sys.stderr)
-            graph = graph_many = graph_plain = None
+            graph = graph_tail = graph_many = graph_plain = None
             batch.set_dispatch_order(True)
             if gather is not None:
                 done[0] = done[1] = None
 
-    def region(r):
+    def region(steps=K):
+        """`steps` launches (a region: K; a ramp unit: C), the t-th with action batch Wm + t % C, captured or eager alike."""
         if graph is not None:
-            graph.replay()
+            for _ in range(steps // C):
+                graph.replay()
+            if steps % C:
+                graph_tail.replay()
         else:
-            for i in range(Wm + r * K, Wm + (r + 1) * K):
-                step(i)
+            for t in range(steps):
+                step(Wm + t % C)
             join_side()
 
-    def restore_snapshot():
-        for k, v in snap.items():  # back to the state the regions are defined to start from
-            batch.planes[k].copy_(v)
-        batch.rec.copy_(snap_rec)
-        batch.cnt.copy_(snap_cnt)
-
-    # untimed clock ramp (the chip idles at low clocks before the first launch): the region's own launches, ~80 ms of them
+    # untimed clock ramp (the chip idles at low clocks before the first launch): the region's own first C launches, ~80 ms of them, and
+    # the remainder graph once (its first replay uploads it); on the freshly reset state, which a second reset puts back (every env
+    # re-initialised from its task, as by the first; copying a 64 MB snapshot back instead leaves that much freshly written data in the
+    # caches: +4 us on the next 20 launches)
     t_ramp, r = time.perf_counter(), 0
-    n_ramp = max(2, min(50, 4000 // max(K, 1)))  # (a fixed count when ranks must stay in step with each other)
+    n_ramp = max(2, min(50, 4000 // C))  # (a fixed count when ranks must stay in step with each other)
     while not a.no_ramp and ((time.perf_counter() - t_ramp < 0.08) if dist is None else (r < n_ramp)):
-        region(r)
+        region(C)
         r += 1
         torch.cuda.synchronize(dev)
-    restore_snapshot()
+    if not a.no_ramp and graph_tail is not None:
+        graph_tail.replay()
+    batch.reset()
+
+    # ---- untimed: W warm-up steps, right before the clock ---------------------------------------------------------
+    for i in range(Wm):
+        step(i)
+    join_side()
     torch.cuda.synchronize(dev)
 
     # ---- R timed regions of exactly K steps, each bracketed by barrier + synchronize ---------------------------
     # Clock of a region: the HIP events recorded on the launch stream right inside the two synchronisations when the region
-    # is ONE hipGraph replay (device time of exactly the K steps), the host clock otherwise.  The host figure additionally
+    # is hipGraph replays (device time of exactly the K steps), the host clock otherwise.  The host figure additionally
     # holds one graph-launch submission and one wake-up (~20 us per region, i.e. 17 % of a 20-step region and 1 % of a
     # 400-step one) — it is reported beside it (timing.host_region_ms), never instead of work.
     device_clock = graph is not None
@@ -1371,13 +1418,16 @@ def main():
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
         ev0.record(stream)  # HIP events on the stream the kernel is launched on
-        region(r)
+        region()
         ev1.record(stream)
         wait_gpu(ev1)
         barrier()
         wall.append(time.perf_counter() - t0)
         devt.append(ev0.elapsed_time(ev1) * 1e-3)
         kern.append(devt[-1] / K)
+    if a.dump_outputs and rank == 0:  # (outside the clock: what the last timed step left, before anything else touches the batch)
+        dump_outputs(a.dump_outputs, batch)
+
     def time_graph(g):  # same event clock and the same number of regions as the headline; the state simply keeps evolving
         for w_ in range(3):
             g.replay()
@@ -1412,26 +1462,31 @@ def main():
             rccl = ".".join(str(v) for v in torch.cuda.nccl.version())
         except Exception:  # noqa: BLE001
             rccl = "?"
-        print(f"bench: rank {rank}/{dist.get_world_size()} backend={dist.get_backend()} RCCL {rccl} device={dev} ({torch.cuda.get_device_name(dev)}) "
-              f"envs [{rank * n}, {(rank + 1) * n}) median region {float(np.median(devt if device_clock else wall)) * 1e3:.4f} ms", file=sys.stderr, flush=True)
+        # (ONE write per line: ranks share the stderr pipe, and an unbuffered stream writes print()'s text and its newline separately)
+        sys.stderr.write(f"bench: rank {rank}/{dist.get_world_size()} backend={dist.get_backend()} RCCL {rccl} device={dev} ({torch.cuda.get_device_name(dev)}) "
+                         f"envs [{rank * n}, {(rank + 1) * n}) median region {float(np.median(devt if device_clock else wall)) * 1e3:.4f} ms\n")
+        sys.stderr.flush()
     elapsed = float(wall_t.median())
     kernel_avg_s = float(np.median(kern))
     status = batch.status()
     assert status == 0, f"device status {status}"
     total_steps = K * n * world
 
-    # ---- bytes of the K launches of region 0, counted by the kernel itself: restore the snapshot and replay them (untimed) with
-    #      the accounting instantiation — algorithmic bytes (the numerator of `frac`) and issued bytes (`traffic`) ----
+    # ---- bytes of the first C launches of region 0, counted by the kernel itself: rebuild its start state (reset + the W warm-up steps)
+    #      and replay them (untimed) with the accounting instantiation — algorithmic bytes (the numerator of `frac`) and
+    #      issued bytes (`traffic`) ----
     roofline = None
-    if rank == 0:
-        restore_snapshot()
+    if rank == 0 and a.full:
+        batch.reset()
+        for i in range(Wm):
+            batch.step_bbox_ptr(bptr[i % S], optr[i % S], FL, sh)
         if gather is not None:
             batch.set_packed_output(packed2[0])
 
         def replay_region0(sh_):  # (the accounting instantiation hands out envs in index order: the bytes do not depend on the order)
-            for i in range(Wm, Wm + K):
+            for i in range(Wm, Wm + C):
                 batch.step_bbox_ptr(bptr[i % S], optr[i % S], FL, sh_)
-        per_launch_bytes, issued_bytes, _ = counted_bytes(batch, replay_region0, K, dev)
+        per_launch_bytes, issued_bytes, _ = counted_bytes(batch, replay_region0, C, dev)
         grp = "|grouped" if batch.orders_itself("bbox", FL) else ""
         kname = {"c3": f"arcle_step_kernel<bbox, FULL, 0, 0, autoreset|elide{grp}, 30>",
                  "c4": f"arcle_step_kernel<bbox, FULL, 0, 0, autoreset|elide|pack{grp}, 30> (fused packed-row epilogue; a multi-rank run has the all-gather inside the event pair)"}.get(a.config, "arcle_step_kernel")
@@ -1452,7 +1507,7 @@ def main():
             f_["frac"] = per_launch_bytes / (f_["avg_launch_us"] * 1e-6) / HBM_PEAK
 
     multi = None
-    if dist is not None and world > 1 and a.config == "c3" and not a.no_multi:
+    if a.full and dist is not None and world > 1 and a.config == "c3" and not a.no_multi:
         try:
             multi = multi_legs(dev, dist, world, rank, shared_gpu, K=4 if shared_gpu else 20, R=2 if shared_gpu else 3)
         except Exception as exc:  # noqa: BLE001 - (a local failure after the agreement point; the headline line is still printed)
@@ -1474,7 +1529,8 @@ def main():
             "timing": {"regions": R, "stat": "median region, max over ranks per region",
                        "clock": "HIP events on the launch stream, recorded between the region's two synchronisations" if device_clock else "host perf_counter between the region's two synchronisations",
                        "host_region_ms": [round(x * 1e3, 4) for x in wall][:12],
-                       "launch": "hipGraph of the K step launches (K arcle_step_bbox calls), one replay per region" if graph is not None else "eager",
+                       "launch": ("hipGraph of the K step launches (K arcle_step_bbox calls), one replay per region" if graph_tail is None and K == C
+                                  else f"hipGraphs of {C} + {K % C} step launches, {K // C} + {int(K % C > 0)} replays per region") if graph is not None else "eager",
                        "region_ms": [round(float(x) * 1e3, 4) for x in wall_t.tolist()][:12]},
             "forms": forms,
             "roofline": roofline,
@@ -1485,12 +1541,12 @@ def main():
                                  "data_path": "none (envs are independent)" if gather is None else "one all_gather_into_tensor of the packed rows per step"}
         if multi is not None:
             out["multi"] = multi
-        if a.config == "c5":
+        if a.full and a.config == "c5":
             seeds = [(int(bbox_np[0, e, 0]), int(bbox_np[0, e, 1])) for e in range(n) if 10 <= op_np[0, e] < 20]
             grids = [tasks[0][e] for e in range(n) if 10 <= op_np[0, e] < 20]
             out["floodfill"] = {"share_of_actions": float(((op_np >= 10) & (op_np < 20)).mean()),
                                 "frontier_rounds": frontier_rounds_sample(grids, seeds)}
-        if world == 1 and not a.no_extras and a.config == "c3":
+        if a.full and world == 1 and not a.no_extras and a.config == "c3":
             ex = {}
             for name, leg in (("vec_api", lambda: vec_api_leg(dev, n, bbox, op)),
                               ("research_env", lambda: research_env_leg(dev, n, bbox, op)),
@@ -1507,12 +1563,12 @@ def main():
                     ex[name] = {"error": f"{type(exc).__name__}: {exc}"}
                 torch.cuda.empty_cache()
             out["extras"] = ex
-        if world == 1 and not a.no_cpu_baseline and a.config == "c3":
-            sustain = Sustained(graph, dev, K * n, K * kernel_avg_s * 1e6) if graph is not None else None
+        if a.full and world == 1 and not a.no_cpu_baseline and a.config == "c3":
+            sustain = Sustained(graph, dev, C * n, C * kernel_avg_s * 1e6) if graph is not None else None
             out["cpu_baseline"] = cpu_baseline(1000, sustain)
             if sustain is not None:
                 out["sustained"] = sustain.result()
-        emit(out, a)
+        emit(out)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

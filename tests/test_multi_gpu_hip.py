@@ -169,7 +169,7 @@ def test_bench_all_gpus_over_rccl_as_the_driver_launches_it(cfg):
         pytest.skip("needs at least two GPUs (the driver's multi-GPU tier)")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "20", "--warmup", "5",
-           "--config", cfg, "--no-cpu-baseline", "--no-extras"]
+           "--config", cfg, "--full", "--no-cpu-baseline", "--no-extras"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)

@@ -403,7 +403,7 @@ def test_bench_two_ranks_on_one_gpu(cfg):
     import torch
     if torch.cuda.device_count() != 1:
         pytest.skip("the shared-GPU leg is for one-GPU boxes")
-    out, p = _bench(["--gpus", "2", "--steps", "6", "--warmup", "2", "--config", cfg, "--regions", "3", "--no-cpu-baseline", "--no-extras"])
+    out, p = _bench(["--gpus", "2", "--steps", "6", "--warmup", "2", "--config", cfg, "--regions", "3", "--full", "--no-cpu-baseline", "--no-extras"])
     assert out["n_gpus"] == 2 and out["steps"] == 6 and out["warmup"] == 2 and out["scaling"] == "weak"
     assert out["config"]["global_envs"] == 2 * out["config"]["envs_per_gpu"] == 16384
     c = out["collective"]
@@ -427,7 +427,7 @@ def test_bench_two_ranks_on_one_gpu(cfg):
 def test_bench_one_rank_is_the_same_line_with_and_without_a_launcher():
     """SCALE(N = 1) is BENCH: `python bench.py --gpus 1` and the driver's torchrun form run the same code path and print the same keys
     (no process group, no `collective` block), and the stdout of either ends in the compact line."""
-    args = ["--gpus", "1", "--steps", "8", "--warmup", "2", "--regions", "3", "--no-cpu-baseline", "--no-extras"]
+    args = ["--gpus", "1", "--steps", "8", "--warmup", "2", "--regions", "3", "--full", "--no-cpu-baseline", "--no-extras"]
     plain, _ = _bench(args)
     launched, _ = _bench(args, launcher=[sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                                          "--master-port", "29533"])
@@ -438,3 +438,42 @@ def test_bench_one_rank_is_the_same_line_with_and_without_a_launcher():
     assert plain["forms"]["step_many"]["value"] > 0 and plain["forms"]["dispatch_order_off"]["value"] > 0
     assert plain["roofline"]["kernel"].startswith("arcle_step_kernel<bbox, FULL, 0, 0, autoreset|elide|grouped, 30>")
     assert plain["roofline"]["plan"]["orders_itself"] is True
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_the_last_one_vs_oracle(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times exactly K steps (one region) and measures nothing else; --dump-outputs writes
+    what the last timed step left, float32 / float64 under 64 MB, the same files from run to run — and equal to the oracle stepping all
+    8192 envs through the W warm-up and K timed action batches of bench's own streams."""
+    import bench
+    K, Wm, n = 8, 3, 8192
+    runs = []
+    for r in range(2):
+        d = tmp_path / f"run{r}"
+        out, _ = _bench(["--gpus", "1", "--steps", str(K), "--warmup", str(Wm), "--dump-outputs", str(d)])
+        assert out["steps"] == K and out["warmup"] == Wm and out["timing"]["regions"] == 1
+        assert out["unit"] == "env-steps/s" and out["higher_is_better"] is True and out["dtype"] == "int8" and out["metric"].startswith("env-steps/sec")
+        assert out["value"] > 0 and abs(out["value"] - K * n / (out["ms_per_step"] * K * 1e-3)) / out["value"] < 1e-3
+        for k in ("roofline", "forms", "cpu_baseline", "sustained", "legs_us_per_step", "multi"):
+            assert k not in out, f"a plain run must not measure `{k}`"
+        files = sorted(os.listdir(d))
+        arrays = {f[:-4]: np.load(d / f) for f in files}
+        assert all(f.endswith(".npy") for f in files) and all(v.dtype in (np.float32, np.float64) for v in arrays.values())
+        assert sum(v.nbytes for v in arrays.values()) <= 64 << 20
+        runs.append(arrays)
+    assert runs[0].keys() == runs[1].keys() and all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0]), "same arguments, different outputs"
+    got = runs[0]
+    assert np.array_equal(got["env_index"], np.arange(n))
+    S = bench.staged_batches(K, Wm)
+    tasks = bench.make_tasks(n, 1000)
+    bb_np, op_np = bench.make_actions(S, n, 2000)
+    orc = _oracle_for(np.arange(n), tasks, 30, 30, -1, "o2arc", O.o2arc_ops())
+    for i in range(Wm + K):
+        rew, trm = orc.step("bbox", bb_np[i % S], op_np[i % S], O.STEP_AUTORESET)
+    assert np.array_equal(got["reward"], rew) and np.array_equal(got["terminated"], trm), "reward / terminated of the last step"
+    assert np.array_equal(got["grid"], orc.get("grid")) and np.array_equal(got["counters"], orc.counters())
+    pidx = got["plane_env_index"].astype(np.int64)
+    for f in ("selected", "clip", "object", "object_sel", "background"):
+        assert np.array_equal(got[f], orc.get(f)[pidx]), f
+    for f in ("grid_dim", "clip_dim", "object_dim", "object_pos", "trials_remain", "terminated", "active", "rotation_parity"):
+        want = orc.get(f)
+        assert np.array_equal(got["rec_" + f], want.reshape(got["rec_" + f].shape)), f

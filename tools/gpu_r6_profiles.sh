@@ -9,18 +9,18 @@ mkdir -p $O
 cd $R
 echo "== smoke"; timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $O/round6_smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/round6_smoke.log | cut -c1-200
 echo "== pytest gpu"; timeout 1700 python -m pytest tests -m gpu -q --maxfail=20 --tb=short > $O/round6_pytest_gpu.log 2>&1; echo "rc=$?"; grep -E "passed|failed" $O/round6_pytest_gpu.log | tail -2
-echo "== bench (default)"; timeout 900 python bench.py > $O/round6_bench.json 2>$O/bench.err; echo "rc=$?"; tail -c 700 $O/round6_bench.json
+echo "== bench (default)"; timeout 900 python bench.py --full > $O/round6_bench.json 2>$O/bench.err; echo "rc=$?"; tail -c 700 $O/round6_bench.json
 grep '^BENCH_FULL ' $O/bench.err | cut -c12- > $O/round6_bench_full.json
-echo "== bench (driver form)"; timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/round6_bench_k20.json 2>$O/bench_k20.err; tail -c 500 $O/round6_bench_k20.json
-echo "== bench --gpus 2 on one GPU (gloo; c3 + the bounded c4 / c5 legs)"; timeout 900 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline > $O/round6_bench_gpus2_shared.json 2>$O/bench_g2.err; tail -c 900 $O/round6_bench_gpus2_shared.json
+echo "== bench (driver form)"; timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/round6_bench_k20.json 2>$O/bench_k20.err; tail -c 500 $O/round6_bench_k20.json
+echo "== bench --gpus 2 on one GPU (gloo; c3 + the bounded c4 / c5 legs)"; timeout 900 python bench.py --gpus 2 --steps 20 --warmup 5 --full --no-cpu-baseline > $O/round6_bench_gpus2_shared.json 2>$O/bench_g2.err; tail -c 900 $O/round6_bench_gpus2_shared.json
 echo "== rocprof kernel trace of the same command"
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/prof
-timeout 900 rocprofv3 --kernel-trace --stats -d $O/prof -o step -- python $R/bench.py --no-cpu-baseline --no-extras > $O/rocprof.log 2>&1; echo "rocprof rc=$?"
+timeout 900 rocprofv3 --kernel-trace --stats -d $O/prof -o step -- python $R/bench.py --full --regions 5 --no-cpu-baseline --no-extras > $O/rocprof.log 2>&1; echo "rocprof rc=$?"
 (python $R/tools/prof_summary.py $O/prof/step_results.db --timed 400 5; tail -1 $O/rocprof.log | cut -c1-1200) > $O/round6_bench_kernel_trace.txt 2>&1; head -14 $O/round6_bench_kernel_trace.txt
 echo "== kernel trace of the bench with extras"
 rm -rf $O/prof2
-timeout 900 rocprofv3 --kernel-trace --stats -d $O/prof2 -o ex -- python $R/bench.py --no-cpu-baseline > $O/rocprof2.log 2>&1; echo "rocprof rc=$?"
+timeout 900 rocprofv3 --kernel-trace --stats -d $O/prof2 -o ex -- python $R/bench.py --full --no-cpu-baseline > $O/rocprof2.log 2>&1; echo "rocprof rc=$?"
 python $R/tools/prof_summary.py $O/prof2/ex_results.db > $O/round6_extras_kernel_trace.txt 2>&1; head -30 $O/round6_extras_kernel_trace.txt
 echo "== PMC passes"
 bash $R/tools/gpu_pmc.sh 2>&1 | tee $O/round6_pmc_summary.txt | tail -40

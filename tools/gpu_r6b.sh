@@ -13,4 +13,4 @@ for rep in 1 2; do
   timeout 300 python tools/researchbench.py 2>&1 | grep -v amdgpu.ids | tail -1
   ARCLE_HIP_LIB=$R/gpurun_lib_sgpr96.so timeout 300 python tools/researchbench.py 2>&1 | grep -v amdgpu.ids | tail -1
 done | tee $O/r6b_research_sgpr.txt
-echo "== bench"; timeout 900 python bench.py > $O/r6b_bench.json 2>$O/r6b_bench.err; echo "rc=$?"; tail -c 900 $O/r6b_bench.json
+echo "== bench"; timeout 900 python bench.py --full > $O/r6b_bench.json 2>$O/r6b_bench.err; echo "rc=$?"; tail -c 900 $O/r6b_bench.json
