@@ -235,6 +235,9 @@ ARCLE_DEV uint32_t eq16(const U4& v, uint32_t byte) {  // bytes == byte
   const uint32_t c = (byte & 0xffu) * 0x01010101u;
   return flags16(nzflags(v[0] ^ c), nzflags(v[1] ^ c), nzflags(v[2] ^ c), nzflags(v[3] ^ c)) ^ 0xffffu;
 }
+ARCLE_DEV bool u4_ne(const U4& a, const U4& b) {  // any byte differs
+  return ((a[0] ^ b[0]) | (a[1] ^ b[1]) | (a[2] ^ b[2]) | (a[3] ^ b[3])) != 0u;
+}
 ARCLE_DEV uint32_t u4_byte(const U4& v, int k) {  // dynamic byte extract
   uint32_t w = (k & 8) ? ((k & 4) ? v[3] : v[2]) : ((k & 4) ? v[1] : v[0]);
   return (w >> (8 * (k & 3))) & 0xffu;
@@ -376,6 +379,24 @@ struct Wave {
     } else {
       store_hbm(pl, v);
     }
+  }
+  // The same where a lane's 16 bytes in memory are PROVABLY `v` already unless `pred` holds: only the lanes with `pred` issue
+  // their store (v_cmp + a branch around the write-through store; the other lanes are masked off in exec).  Callers derive `pred`
+  // from what the wave holds of the plane as it is in memory (new != old) or from the op's geometry; never from a guess.  The
+  // plane still counts as written by the step (`stored`: dense reward, incremental rows) and the resident forms keep the whole value.
+  // issued: 16 B per lane that stored.
+  ARCLE_DEV void store_if(int pl, const U4& v, bool pred) const {
+    if (resident) {
+      store(pl, v);
+      return;
+    }
+    stored |= 1u << pl;
+    const bool st = live && pred;
+    if (st) {
+      if (store_nt) xl::store16_nt(p.plane[pl], poff, v);
+      else xl::store16(p.plane[pl], poff, v);
+    }
+    if (count) issued += 16u * (uint32_t)__builtin_popcountll(xl::ballot(st));
   }
 
   // ---- 16-bit cell mask -> 16 byte masks (0x00 / 0xff), through the workgroup's LDS table ----------
@@ -727,6 +748,13 @@ ARCLE_DEV void need_grid(const Wave& w, Scratch& s) {
   }
 }
 
+// The op's new grid plane.  `old` is what the step holds of the plane as it is in memory (s.grid before the op changed it), valid
+// iff `known`: a lane whose 16 bytes did not change stores nothing (4 XORs, 3 ORs and a compare against a 16 B write-through store);
+// without a known old value every lane stores.
+ARCLE_DEV void store_grid(const Wave& w, const U4& v, const U4& old, bool known) {
+  w.store_if(ARCLE_PL_GRID, v, !known || u4_ne(v, old));
+}
+
 // grid[:gh,:gw] == answer with equal dims (base.py:176-177, o2arcenv.py:124-127)
 template <int ACCT>
 ARCLE_DEV bool grid_equals_answer(const Wave& w, Scratch& s, const Rec& r) {
@@ -747,11 +775,15 @@ ARCLE_DEV bool grid_equals_answer(const Wave& w, Scratch& s, const Rec& r) {
 
 // _apply_patch + _apply_sel (object.py:113-165).  `tile` holds the object plane staged in LDS with an
 // extra flat offset `S0` (object cell f lives at tile[f + S0]); `osel` is the object_sel cell mask in
-// the same shifted frame.  Writes grid and selected.
+// the same shifted frame.  Writes grid and selected: the grid only where it changed when the step holds the plane as it is in
+// memory (a fresh selection: the lift loaded it), `selected` only inside the placed rectangle when the plane is known to be all
+// zero (`sel_zero`: ARCLE_STEP_ELIDE_SELECTED and the env entered the step inactive).
 template <int ACCT>
 ARCLE_DEV void place(const Wave& w, Scratch& s, const Rec& r, const U4& background, const uint32_t* tile, uint32_t osel,
-                     int S0, bool osel_full) {
+                     int S0, bool osel_full, bool sel_zero) {
   const int W = w.p.W;
+  const U4 old = s.grid;
+  const bool known = s.have_grid;
   s.grid = background;
   U4 selected = u4_zero();
   const int ox = r.ox(), oy = r.oy();
@@ -767,8 +799,8 @@ ARCLE_DEV void place(const Wave& w, Scratch& s, const Rec& r, const U4& backgrou
     // object.py:165; when object_sel covers the whole object tile (rectangle selection) the placed mask IS R
     selected = u4_and1(osel_full ? rb : w.expand16(w.shifted_bits(osel, S) & R), 0x01010101u);
   }
-  w.store(ARCLE_PL_GRID, s.grid);
-  w.store(ARCLE_PL_SELECTED, selected);
+  store_grid(w, s.grid, old, known);
+  w.store_if(ARCLE_PL_SELECTED, selected, !sel_zero || u4_ne(selected, u4_zero()));
   s.have_grid = s.grid_counted = true;
   s.sel_pending = 0;
   ARCLE_ACCT(2 * w.p.P);
@@ -1048,7 +1080,7 @@ ARCLE_DEV void op_floodfill(const Wave& w, Scratch& s, const Rec& r, const Sel& 
     vis = to16(w, F);
   }
   s.grid = u4_sel1(w.expand16(vis), ((uint32_t)color & 0xffu) * 0x01010101u, s.grid);
-  w.store(ARCLE_PL_GRID, s.grid);
+  w.store(ARCLE_PL_GRID, s.grid);  // (in full: fills are the longest waves of FloodFill-heavy mixes, and a predicated store there measured slower)
   ARCLE_ACCT(p.P);
 }
 
@@ -1401,6 +1433,7 @@ ARCLE_DEV StepOut step_core(const Wave& w, Rec& r, I2& cnt0, const U4& payload, 
   s.have_grid = false;
   s.grid_counted = false;
   s.loaded = false;
+  s.grid = u4_zero();
   if (early) {  // (streaming instantiation: the plane was requested beside the per-env scalars and is in registers by now)
     s.grid = early_grid;
     s.have_grid = true;
@@ -1449,6 +1482,8 @@ ARCLE_DEV StepOut step_core(const Wave& w, Rec& r, I2& cnt0, const U4& payload, 
   // with ARCLE_STEP_ELIDE_SELECTED an env that enters the step inactive is known to hold an all-zero `selected`
   // plane already (see include/arcle_hip.h): the zero-fill would rewrite zeros with zeros
   const uint32_t zero_selected = (flags & ARCLE_STEP_ELIDE_SELECTED) ? (r.w[ARCLE_REC_ACTIVE >> 2] & rs_mask) : rs_mask;
+  // ... by the same invariant an object op that lifts a fresh selection stores `selected` only inside the placed rectangle (place)
+  const bool sel_zero = (flags & ARCLE_STEP_ELIDE_SELECTED) && (r.w[ARCLE_REC_ACTIVE >> 2] & 0xffu) == 0u;
   if (ACCT && rs_mask) ARCLE_ACCT(P);  // semantic accounting is unchanged
   r.w[ARCLE_REC_ACTIVE >> 2] &= ~rs_mask;
   if ((oflags & (ARCLE_OPF_KEEP_SEL | ARCLE_OPF_RESET_SEL)) == ARCLE_OPF_KEEP_SEL) ARCLE_ACCT(P);  // object.py:36-40
@@ -1475,7 +1510,7 @@ ARCLE_DEV StepOut step_core(const Wave& w, Rec& r, I2& cnt0, const U4& payload, 
       const int dx = (arg == 0) ? -1 : (arg == 1) ? 1 : 0;
       const int dy = (arg == 2) ? 1 : (arg == 3) ? -1 : 0;
       r.put2(ARCLE_REC_OBJECT_POS, r.ox() + dx, r.oy() + dy);  // :238, int8 wrap
-      place<ACCT>(w, s, r, L.background, w.lds->a, L.osel, L.S0, L.osel_full);
+      place<ACCT>(w, s, r, L.background, w.lds->a, L.osel, L.S0, L.osel_full, sel_zero);
       break;
     }
     case ARCLE_OP_ROTATE:
@@ -1569,7 +1604,7 @@ ARCLE_DEV StepOut step_core(const Wave& w, Rec& r, I2& cnt0, const U4& payload, 
         // Flip D0/D1 leave object_dim = (h,w) while the tile is (w,h) (:270-273): only when the two agree is the
         // placed selection exactly the destination rectangle
         place<ACCT>(w, s, r, background, w.lds->a, rect_sel ? orect : nz16(object_sel), 0,
-                    rect_sel && nh == r.oh() && nw == r.ow());
+                    rect_sel && nh == r.oh() && nw == r.ow(), sel_zero);
         break;
       }
       Lift L;
@@ -1584,7 +1619,7 @@ ARCLE_DEV StepOut step_core(const Wave& w, Rec& r, I2& cnt0, const U4& payload, 
       }
       if (!L.fresh) ARCLE_ACCT(2 * P);  // object, object_sel written back (already counted when fresh)
       w.stage(w.lds->a, L.object);
-      place<ACCT>(w, s, r, L.background, w.lds->a, nz16(L.object_sel), 0, false);
+      place<ACCT>(w, s, r, L.background, w.lds->a, nz16(L.object_sel), 0, false, sel_zero);
       break;
     }
     case ARCLE_OP_COPY: {  // object.py:291-312
@@ -1620,31 +1655,38 @@ ARCLE_DEV StepOut step_core(const Wave& w, Rec& r, I2& cnt0, const U4& payload, 
       const U4 pc = w.shifted(w.lds->a, -(sel.x0 * W + sel.y0));
       uint32_t R = w.rect16(sel.x0, ex - 1, sel.y0, ey - 1);
       if (!arg) R &= pos16(pc);  // paste_blank=False: where=(patch>0)
+      const U4 old = s.grid;
       s.grid = u4_sel(w.expand16(R), pc, s.grid);
-      w.store(ARCLE_PL_GRID, s.grid);
+      store_grid(w, s.grid, old, true);
       ARCLE_ACCT(P);
       break;
     }
     case ARCLE_OP_COPY_FROM_INPUT: {  // critical.py:28-29
+      const U4 old = s.grid;
+      const bool known = s.have_grid;  // (only the streaming instantiations hold the grid here: their early request)
       s.grid = w.load(ARCLE_PL_INPUT);
       s.have_grid = s.grid_counted = true;
-      w.store(ARCLE_PL_GRID, s.grid);
+      store_grid(w, s.grid, old, known);
       r.w[0] = (r.w[0] & 0xffffu) | (r.w[0] << 16);  // grid_dim = input_dim
       ARCLE_ACCT(2 * P);
       break;
     }
     case ARCLE_OP_RESET_GRID: {  // critical.py:17
+      const U4 old = s.grid;
+      const bool known = s.have_grid;
       s.grid = u4_zero();
       s.have_grid = s.grid_counted = true;
-      w.store(ARCLE_PL_GRID, s.grid);
+      store_grid(w, s.grid, old, known);
       ARCLE_ACCT(P);
       break;
     }
     case ARCLE_OP_RESIZE_GRID: {  // critical.py:39-46
       if (!sel.any_nz) break;
+      const U4 old = s.grid;
+      const bool known = s.have_grid;
       s.grid = u4_zero();
       s.have_grid = s.grid_counted = true;
-      w.store(ARCLE_PL_GRID, s.grid);
+      store_grid(w, s.grid, old, known);
       r.put2(ARCLE_REC_GRID_DIM, sel.x1 - sel.x0 + 1, sel.y1 - sel.y0 + 1);
       ARCLE_ACCT(P);
       break;
@@ -1654,8 +1696,9 @@ ARCLE_DEV StepOut step_core(const Wave& w, Rec& r, I2& cnt0, const U4& payload, 
       need_grid<ACCT>(w, s);
       const int h = sel.x1 - sel.x0 + 1, wd = sel.y1 - sel.y0 + 1;
       w.stage(w.lds->a, sel.is_rect ? s.grid : u4_and(s.grid, w.expand16(sel_nz(w, sel))));
+      const U4 old = s.grid;
       s.grid = u4_and(w.shifted(w.lds->a, sel.x0 * W + sel.y0), w.expand16(w.rect16(0, h - 1, 0, wd - 1)));
-      w.store(ARCLE_PL_GRID, s.grid);
+      store_grid(w, s.grid, old, true);
       r.put2(ARCLE_REC_GRID_DIM, h, wd);
       ARCLE_ACCT(P);
       break;
@@ -1664,8 +1707,9 @@ ARCLE_DEV StepOut step_core(const Wave& w, Rec& r, I2& cnt0, const U4& payload, 
       need_grid<ACCT>(w, s);
       const int ah = r.ah(), aw = r.aw();
       r.put2(ARCLE_REC_GRID_DIM, ah, aw);
+      const U4 old = s.grid;
       s.grid = u4_and(s.grid, w.expand16(w.rect16(0, ah - 1, 0, aw - 1)));
-      w.store(ARCLE_PL_GRID, s.grid);
+      store_grid(w, s.grid, old, true);
       ARCLE_ACCT(P);
       break;
     }

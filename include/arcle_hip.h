@@ -117,7 +117,9 @@ enum arcle_op_kind {
 /* reset_sel (object.py:20-25) need not rewrite a `selected` plane that is already zero.  Whenever the op table holds
  * no keep_sel-wrapped op, `active == 0` implies `selected == 0` (object ops set both, reset_sel / init_state clear both,
  * nothing else writes `selected`), so with this flag the zero-fill is skipped when the env enters the step with
- * active == 0.  The state after the step is bit-identical; only a redundant 1-plane write disappears.  Do NOT set it
+ * active == 0, and an object op that lifts a fresh selection in such an env stores `selected` only in the 16-byte chunks
+ * the placed object covers (the rest is zero already).  The state after the step is bit-identical; only redundant writes
+ * disappear.  Do NOT set it
  * for states written from outside (e.g. a state dict uploaded for transition()) that may violate the invariant;
  * arcle_set_op_table() reports through arcle_can_elide_selected() whether the installed table permits it. */
 #define ARCLE_STEP_ELIDE_SELECTED 2u
