@@ -50,24 +50,9 @@ ARCLE_DEV int lds_idx(int i, int /*n*/) { return i; }
 // Wave-uniform loads of per-env scalars (record, op index, counters, bbox / point payload): the address is uniform and
 // the location is not written by anyone else during the launch, so they go through the scalar cache straight into
 // SGPRs (s_load_dword[x2|x4]) — no VGPRs, no v_readfirstlane, handled by the scalar ALU afterwards.
-#ifdef ARCLE_VECTOR_INPUTS  // A/B: the same values through the vector memory path (global_load + v_readfirstlane)
-ARCLE_DEV uint32_t uload1(const void* p) { return uniform(*reinterpret_cast<const ARCLE_AS_GLOBAL uint32_t*>((uintptr_t)p)); }
-ARCLE_DEV U2 uload2(const void* p) {
-  U2 v = *reinterpret_cast<const ARCLE_AS_GLOBAL U2*>((uintptr_t)p);
-  v[0] = uniform(v[0]);
-  v[1] = uniform(v[1]);
-  return v;
-}
-ARCLE_DEV U4 uload4(const void* p) {
-  U4 v = *reinterpret_cast<const ARCLE_AS_GLOBAL U4*>((uintptr_t)p);
-  for (int i = 0; i < 4; i++) v[i] = uniform(v[i]);
-  return v;
-}
-#else
 ARCLE_DEV uint32_t uload1(const void* p) { return *reinterpret_cast<const ARCLE_AS_CONST uint32_t*>((uintptr_t)p); }
 ARCLE_DEV U2 uload2(const void* p) { return *reinterpret_cast<const ARCLE_AS_CONST U2*>((uintptr_t)p); }
 ARCLE_DEV U4 uload4(const void* p) { return *reinterpret_cast<const ARCLE_AS_CONST U4*>((uintptr_t)p); }
-#endif
 // 16 B plane load: SGPR base + 32-bit VGPR byte offset (global_load_dwordx4 v, v_off, s[base])
 ARCLE_DEV U4 load16(const int8_t* base, uint32_t off) {
   return *reinterpret_cast<const ARCLE_AS_GLOBAL U4*>((uintptr_t)base + off);
@@ -183,10 +168,6 @@ ARCLE_DEV void arrived(U4& a, U2& b, uint32_t& c, U4& d) { asm volatile("" : "+s
 ARCLE_DEV void arrived3(U4& a, U2& b, uint32_t& c) { asm volatile("" : "+s"(a), "+s"(b), "+s"(c)); }
 #ifndef ARCLE_STOP_AT
 #define ARCLE_STOP_AT 0
-#endif
-#ifndef ARCLE_PACK_SPEC
-#define ARCLE_PACK_SPEC 0  // 1: packed-row instantiations also request the grid plane beside the per-env scalar loads — every wave needs it for
-                           // its row, yet it loses (c4 6.57 -> 6.62 us, hinted 6.21 -> 6.50: profiles/round4_experiments.txt); kept as a knob
 #endif
 #ifndef ARCLE_SPEC_SMALL_MAX
 #define ARCLE_SPEC_SMALL_MAX 2048  // (0 = off) batches up to this size take the speculative grid load as well: one latency chain per launch
@@ -429,11 +410,6 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) __attribute__((amdgpu_num_sgpr(A
   if (STREAM) {
     const uint32_t goff = (uint32_t)env * (uint32_t)ARCLE_MAX_CELLS + 16u * (threadIdx.x & 63u);
     early_grid = (FL & ARCLE_STEPX_EARLY_NT) ? xl::load16_nt(reinterpret_cast<const int8_t*>(order), goff) : xl::load16(reinterpret_cast<const int8_t*>(order), goff);
-    early = true;
-  } else if (ARCLE_PACK_SPEC && FL >= 0 && (FL & ARCLE_STEP_PACK_OBS) && WC == 30) {
-    // fused packed rows: EVERY wave needs the grid plane at its end (the row it packs), so the speculative request is never wasted —
-    // and the epilogue no longer waits for a read-back
-    early_grid = xl::load16(pa.plane[ARCLE_PL_GRID], (uint32_t)env * (uint32_t)ARCLE_MAX_CELLS + 16u * (threadIdx.x & 63u));
     early = true;
   } else if (WC == 0 && !ACCT && !FEAT && ING != arcle::INGRESS_BBOX5_PF) {
     // small batches of other grid shapes (at most a wave or two per SIMD: the launch is one wave's latency chain, nothing competes for
@@ -949,14 +925,6 @@ static int width_class(const StepParams& p) {
   if (p.W < 16 || p.W > 32) return arcle::FW_GENERIC;
   return p.PS == ARCLE_MAX_CELLS ? arcle::FW_FULL : arcle::FW_FAST;
 }
-#define STEP_ARGS (const int8_t*)p.rec, (const int32_t*)p.cnt, p.op, p.sel, (const uint32_t*)nullptr, p.n_envs, p.wpw, g.x >> 3, p
-#define STEP_LDS(b) ((size_t)((b).x / 64u) * sizeof(arcle::WaveLDS))
-#define LAUNCH_STEP(...) hipLaunchKernelGGL((arcle_step_kernel<__VA_ARGS__>), g, b, STEP_LDS(b), st, STEP_ARGS)
-// a launch that orders itself: the preloaded `order` argument carries the object-op mask, `n_envs` the reciprocal of the group count
-#define LAUNCH_GROUPED(INGV, FWV, FLSET, FEATV)                                                                                             \
-  hipLaunchKernelGGL((arcle_step_kernel<INGV, FWV, 0, FEATV, (FLSET) | ARCLE_STEPX_GROUPED, 30>), g, b, STEP_LDS(b), st, (const int8_t*)p.rec,    \
-                     (const int32_t*)p.cnt, p.op, p.sel, reinterpret_cast<const uint32_t*>((uintptr_t)p.long_mask), (int)p.group_magic, __builtin_ctz((unsigned)p.wpw), \
-                     (uint32_t)p.n_envs >> 3, p)
 // the flag combination ARCVecEnv steps with (next-step autoreset, elided zero-fill of `selected`) has its own instantiation
 // with the flags as a compile-time constant
 static constexpr int HOT_FLAGS = ARCLE_STEP_AUTORESET | ARCLE_STEP_ELIDE_SELECTED;
@@ -967,111 +935,138 @@ static constexpr int HOT_PACK_FLAGS = HOT_FLAGS | ARCLE_STEP_PACK_OBS;
 static constexpr int RESEARCH_FLAGS = ARCLE_STEP_ELIDE_SELECTED | ARCLE_STEP_TRUNCATE | ARCLE_STEP_RESAMPLE | ARCLE_STEP_DENSE | ARCLE_STEP_FLAT_OBS;
 static constexpr int RESEARCH_FL = RESEARCH_FLAGS | ARCLE_STEPX_FLAT_FILTERED;
 static constexpr int RESEARCH_INC_FL = RESEARCH_FL | ARCLE_STEP_ROWS_INCREMENTAL;  // ... with incremental rows (what ARCVecEnv runs)
-static bool research_shape(const StepParams& p, uint32_t extra = 0) {
-  return p.flags == ((uint32_t)RESEARCH_FLAGS | extra) && p.flat_filter == 1 && p.flat_tail == 0 && p.flat_stride == ARCLE_ROW30_FILTERED_STRIDE;
-}
-#ifdef ARCLE_FAST_BUILD  // development builds: only the benchmark's instantiations exist (seconds instead of minutes)
-template <int ING>
-static int launch_step_ing(int, bool acct, bool feat, dim3 g, dim3 b, hipStream_t st, const StepParams& p) {
-  if (ING != arcle::INGRESS_BBOX || width_class(p) != arcle::FW_FULL || p.H != 30 || p.W != 30) return ARCLE_ERR_CONFIG;
-  if (feat || acct) {
-    if (!acct && research_shape(p)) LAUNCH_STEP(arcle::INGRESS_BBOX, arcle::FW_FULL, 0, 1, RESEARCH_FL, 30);
-    else if (!acct && research_shape(p, ARCLE_STEP_ROWS_INCREMENTAL)) LAUNCH_STEP(arcle::INGRESS_BBOX, arcle::FW_FULL, 0, 1, RESEARCH_INC_FL, 30);
-    else LAUNCH_STEP(arcle::INGRESS_BBOX, arcle::FW_FULL, 1, 1);
-  } else if (p.flags == (uint32_t)HOT_FLAGS && p.group_magic) {
-    LAUNCH_GROUPED(arcle::INGRESS_BBOX, arcle::FW_FULL, HOT_FLAGS, 0);
-  } else if (p.flags == (uint32_t)HOT_FLAGS && p.spec_grid) {
-#define LAUNCH_STREAM(BITS)                                                                                                                    \
-  hipLaunchKernelGGL((arcle_step_kernel<arcle::INGRESS_BBOX, arcle::FW_FULL, 0, 0, HOT_FLAGS | ARCLE_STEPX_STREAM | (BITS), 30>), g, b, STEP_LDS(b), st, (const int8_t*)p.rec, \
-                     (const int32_t*)p.cnt, p.op, p.sel, (const uint32_t*)p.plane[ARCLE_PL_GRID], p.n_envs, p.wpw, g.x >> 3, p)
-    switch (p.spec_grid) {
-      case 'B': LAUNCH_STREAM(ARCLE_STEPX_STORE_NT); break;
-      case 'H': LAUNCH_STREAM(ARCLE_STEPX_EARLY_NT); break;
-      case 'J': LAUNCH_STREAM(ARCLE_STEPX_STORE_NT | ARCLE_STEPX_EARLY_NT); break;
-      default: LAUNCH_STREAM(0); break;
-    }
-#undef LAUNCH_STREAM
-  } else if (p.flags == (uint32_t)HOT_FLAGS) LAUNCH_STEP(arcle::INGRESS_BBOX, arcle::FW_FULL, 0, 0, HOT_FLAGS, 30);
-  else LAUNCH_STEP(arcle::INGRESS_BBOX, arcle::FW_FULL, 0, 0, -1, 30);
-  return ARCLE_OK;
-}
+
+// The lean instantiations: the standard 30 x 30 grid (FW_FULL, no accounting) with a flag set FL as a compile-time constant.  A row lists,
+// per twin, the ingress forms that have it (bit 1 << ING):
+//   plain     arcle_step_kernel<ING, FW_FULL, 0, FEAT, FL, 30>
+//   grouped   ... FL | ARCLE_STEPX_GROUPED: the launch orders itself (p.group_magic, see plan_launch)
+//   stream    ... FL | ARCLE_STEPX_STREAM | stream_bits(policy), one per policy 'A' 'B' 'H' 'J': the grid plane requested beside the scalars
+//   prefetch  <INGRESS_BBOX5_PF, ...>: the next step's records copied from host memory by the front workgroups (arcle_step_many)
+//   rollout   arcle_rollout_kernel<ING, FW_FAST, 30, FL>
+// A launch takes the first row that matches its flags (-1: a step without feature flags, any rollout) and has a twin that applies, in the
+// order prefetch, grouped, stream, plain.  The flag sets are distinct and -1 comes last, so the lookups of plan_launch (lean_twin) agree.
+// Development builds (-DARCLE_FAST_BUILD: seconds instead of minutes) keep the cells marked DEV, for bbox tuples only, and of the kernels
+// outside the table the feature / accounting one of the 30 x 30 grid.
+#ifdef ARCLE_FAST_BUILD
+static constexpr bool DEV_BUILD = true;
 #else
-template <int ING, int FW>
-static void launch_step_tbl(bool acct, bool feat, dim3 g, dim3 b, hipStream_t st, const StepParams& p) {
-  if constexpr (FW == arcle::FW_FULL) {  // the standard 30 x 30 grid: lean instantiations with the dimensions as compile-time constants
-    if (p.H == 30 && p.W == 30 && !acct) {
-      if constexpr (ING == arcle::INGRESS_BBOX5) {
-        if (p.flags == (uint32_t)HOT_FLAGS && p.next_sel && p.wpw == WAVES_PER_WG) {  // records prefetched by the launch's front workgroups
-          const dim3 gp(g.x + ARCLE_PF_BLOCKS);
-          hipLaunchKernelGGL((arcle_step_kernel<arcle::INGRESS_BBOX5_PF, FW, 0, 0, HOT_FLAGS, 30>), gp, b, STEP_LDS(b), st, (const int8_t*)p.rec,
-                             (const int32_t*)p.cnt, p.op, p.sel, (const uint32_t*)nullptr, p.n_envs, p.wpw, g.x >> 3, p);
-          return;
-        }
-      }
-      if (p.group_magic && p.flags == (uint32_t)HOT_FLAGS) { LAUNCH_GROUPED(ING, FW, HOT_FLAGS, 0); return; }  // (every ingress form)
-      if constexpr (ING == arcle::INGRESS_BBOX || ING == arcle::INGRESS_BBOX5 || ING == arcle::INGRESS_POINT) {
-        // ... and without the auto-reset: what ARCVecEnv steps with by default (the reference has none: a terminated env keeps being mutated)
-        if (p.group_magic && p.flags == (uint32_t)ARCLE_STEP_ELIDE_SELECTED) { LAUNCH_GROUPED(ING, FW, ARCLE_STEP_ELIDE_SELECTED, 0); return; }
-      }
-      if constexpr (ING == arcle::INGRESS_BBOX || ING == arcle::INGRESS_BBOX5) {
-        if (p.group_magic && p.flags == (uint32_t)HOT_PACK_FLAGS) { LAUNCH_GROUPED(ING, FW, HOT_PACK_FLAGS, 0); return; }
-        if (p.group_magic && research_shape(p, ARCLE_STEP_ROWS_INCREMENTAL)) { LAUNCH_GROUPED(ING, FW, RESEARCH_INC_FL, 1); return; }
-      }
-      if (p.flags == (uint32_t)HOT_PACK_FLAGS) { LAUNCH_STEP(ING, FW, 0, 0, HOT_PACK_FLAGS, 30); return; }
-      if constexpr (ING == arcle::INGRESS_BBOX || ING == arcle::INGRESS_BBOX5) {
-        if (p.flags == (uint32_t)HOT_FLAGS && p.spec_grid) {  // speculative grid request: the plane's base rides in the preloaded `order` argument
-#define LAUNCH_STREAM(BITS)                                                                                                                    \
-  hipLaunchKernelGGL((arcle_step_kernel<ING, FW, 0, 0, HOT_FLAGS | ARCLE_STEPX_STREAM | (BITS), 30>), g, b, STEP_LDS(b), st, (const int8_t*)p.rec, (const int32_t*)p.cnt, \
-                     p.op, p.sel, (const uint32_t*)p.plane[ARCLE_PL_GRID], p.n_envs, p.wpw, g.x >> 3, p)
-          switch (p.spec_grid) {
-            case 'B': LAUNCH_STREAM(ARCLE_STEPX_STORE_NT); break;
-            case 'H': LAUNCH_STREAM(ARCLE_STEPX_EARLY_NT); break;
-            case 'J': LAUNCH_STREAM(ARCLE_STEPX_STORE_NT | ARCLE_STEPX_EARLY_NT); break;
-            default: LAUNCH_STREAM(0); break;
-          }
-#undef LAUNCH_STREAM
-          return;
-        }
-      }
-      if (p.flags == (uint32_t)HOT_FLAGS) { LAUNCH_STEP(ING, FW, 0, 0, HOT_FLAGS, 30); return; }
-      if (research_shape(p)) { LAUNCH_STEP(ING, FW, 0, 1, RESEARCH_FL, 30); return; }
-      if (research_shape(p, ARCLE_STEP_ROWS_INCREMENTAL)) { LAUNCH_STEP(ING, FW, 0, 1, RESEARCH_INC_FL, 30); return; }
-      if (!feat) { LAUNCH_STEP(ING, FW, 0, 0, -1, 30); return; }
+static constexpr bool DEV_BUILD = false;
+#endif
+enum { TW_PLAIN, TW_GROUPED, TW_STREAM, TW_PF, TW_ROLLOUT, N_TWINS };
+static constexpr uint32_t I_MASK = 1u << arcle::INGRESS_MASK, I_BBOX = 1u << arcle::INGRESS_BBOX, I_POINT = 1u << arcle::INGRESS_POINT,
+                          I_BBOX5 = 1u << arcle::INGRESS_BBOX5, I_T5 = I_BBOX | I_BBOX5, I_ANY = I_MASK | I_T5 | I_POINT | (1u << arcle::INGRESS_BITS),
+                          DEV = 1u << 31;
+struct LeanRow {
+  int fl, feat;
+  uint32_t twin[N_TWINS];
+};
+static constexpr LeanRow LEAN[] = {
+    // flag set                FEAT  plain          grouped          stream          prefetch  rollout
+    {HOT_FLAGS,                  0, {I_ANY | DEV,   I_ANY | DEV,     I_T5 | DEV,     I_BBOX5,  I_BBOX | I_POINT | DEV}},
+    {ARCLE_STEP_ELIDE_SELECTED,  0, {0,             I_T5 | I_POINT,  0,              0,        0}},  // (ARCVecEnv without the auto-reset)
+    {HOT_PACK_FLAGS,             0, {I_ANY,         I_T5,            0,              0,        I_BBOX | I_POINT | DEV}},
+    {RESEARCH_FL,                1, {I_ANY | DEV,   0,               0,              0,        0}},
+    {RESEARCH_INC_FL,            1, {I_ANY | DEV,   I_T5,            0,              0,        0}},
+    {-1,                         0, {I_ANY | DEV,   0,               0,              0,        I_MASK | I_BBOX | I_POINT | DEV}},
+};
+static constexpr int N_LEAN = (int)(sizeof(LEAN) / sizeof(LEAN[0]));
+static constexpr bool lean_has(int row, int tw, int ingress) {  // (in this build)
+  const uint32_t c = LEAN[row].twin[tw];
+  return ((DEV_BUILD ? ((c & DEV) ? I_BBOX : 0u) : c) >> ingress) & 1u;
+}
+// does a step run with the flag set (and fused row shape) a row folds in?
+static bool lean_match(int fl, const StepParams& p) {
+  if (fl < 0) return !(p.flags & ARCLE_STEP_FEATURE_FLAGS);
+  if (p.flags != ((uint32_t)fl & 0xffffu)) return false;
+  const int filtered = (fl & ARCLE_STEPX_FLAT_FILTERED) ? 1 : 0;
+  return !(fl & ARCLE_STEP_FLAT_OBS) ||
+         (p.flat_filter == filtered && p.flat_tail == 0 && p.flat_stride == (filtered ? ARCLE_ROW30_FILTERED_STRIDE : ARCLE_ROW30_FULL_STRIDE));
+}
+// can a 30 x 30 step launch without accounting take twin `tw`?
+static bool lean_twin(int tw, int ingress, const StepParams& p) {
+  for (int r = 0; r < N_LEAN; r++)
+    if (lean_has(r, tw, ingress) && lean_match(LEAN[r].fl, p)) return true;
+  return false;
+}
+// calls f(row) with the rows as compile-time constants, in order, until it returns true
+template <int R = 0, class F>
+static bool each_lean(F&& f) {
+  if constexpr (R == N_LEAN) return false;
+  else return f(std::integral_constant<int, R>()) || each_lean<R + 1>(f);
+}
+// the streaming policies' cache hints: 'A' cached request, write-through stores; 'B' non-temporal stores; 'H' non-temporal request; 'J' both
+static constexpr int stream_bits(int policy) {
+  return (policy == 'B' || policy == 'J' ? ARCLE_STEPX_STORE_NT : 0) | (policy == 'H' || policy == 'J' ? ARCLE_STEPX_EARLY_NT : 0);
+}
+
+// One step launch.  The preloaded `order`, `n_envs`, `wpw_front`, `nb8` arguments carry: for a plain launch nullptr, the batch size, the
+// waves per workgroup, the workgroups per XCD; for a launch that orders itself the object-op mask, group_magic, log2 of the waves per
+// workgroup, the slots per XCD; for a streaming one the grid plane's base in `order`.  The record-prefetching form runs ARCLE_PF_BLOCKS
+// copy workgroups in front of the env waves.
+template <int ING, int FW, int ACCT, int FEAT, int FL = -1, int WC = 0>
+static void launch_step_kernel(dim3 g, dim3 b, hipStream_t st, const StepParams& p) {
+  constexpr bool GROUPED = FL >= 0 && (FL & ARCLE_STEPX_GROUPED), STREAM = FL >= 0 && (FL & ARCLE_STEPX_STREAM);
+  const uint32_t* order = GROUPED ? reinterpret_cast<const uint32_t*>((uintptr_t)p.long_mask) : STREAM ? (const uint32_t*)p.plane[ARCLE_PL_GRID] : nullptr;
+  hipLaunchKernelGGL((arcle_step_kernel<ING, FW, ACCT, FEAT, FL, WC>), dim3(g.x + (ING == arcle::INGRESS_BBOX5_PF ? ARCLE_PF_BLOCKS : 0)), b,
+                     (size_t)(b.x / 64u) * sizeof(arcle::WaveLDS), st, (const int8_t*)p.rec, (const int32_t*)p.cnt, p.op, p.sel, order,
+                     GROUPED ? (int)p.group_magic : p.n_envs, GROUPED ? __builtin_ctz((unsigned)p.wpw) : p.wpw,
+                     GROUPED ? (uint32_t)p.n_envs >> 3 : g.x >> 3, p);
+}
+
+template <int ING>
+static bool launch_lean(dim3 g, dim3 b, hipStream_t st, const StepParams& p) {
+  return each_lean([&](auto row) {
+    constexpr int R = decltype(row)::value, FL = LEAN[R].fl, FEAT = LEAN[R].feat, F = arcle::FW_FULL;
+    if (!lean_match(FL, p)) return false;
+    if constexpr (lean_has(R, TW_PF, ING)) {
+      if (p.next_sel && p.wpw == WAVES_PER_WG) return launch_step_kernel<arcle::INGRESS_BBOX5_PF, F, 0, FEAT, FL, 30>(g, b, st, p), true;
     }
-  }
+    if constexpr (lean_has(R, TW_GROUPED, ING)) {
+      if (p.group_magic) return launch_step_kernel<ING, F, 0, FEAT, FL | ARCLE_STEPX_GROUPED, 30>(g, b, st, p), true;
+    }
+    if constexpr (lean_has(R, TW_STREAM, ING)) {
+      constexpr int S = FL | ARCLE_STEPX_STREAM;
+      switch (p.spec_grid) {
+        case 0: break;
+        case 'B': return launch_step_kernel<ING, F, 0, FEAT, S | stream_bits('B'), 30>(g, b, st, p), true;
+        case 'H': return launch_step_kernel<ING, F, 0, FEAT, S | stream_bits('H'), 30>(g, b, st, p), true;
+        case 'J': return launch_step_kernel<ING, F, 0, FEAT, S | stream_bits('J'), 30>(g, b, st, p), true;
+        default: return launch_step_kernel<ING, F, 0, FEAT, S | stream_bits('A'), 30>(g, b, st, p), true;
+      }
+    }
+    if constexpr (lean_has(R, TW_PLAIN, ING)) return launch_step_kernel<ING, F, 0, FEAT, FL, 30>(g, b, st, p), true;
+    return false;
+  });
+}
+
+template <int ING, int FW>
+static int launch_step_tbl(bool acct, bool feat, dim3 g, dim3 b, hipStream_t st, const StepParams& p) {
+  const bool std30 = FW == arcle::FW_FULL && p.H == 30 && p.W == 30;
+  if (std30 && !acct && launch_lean<ING>(g, b, st, p)) return ARCLE_OK;
   // the feature instantiation also carries the byte accounting (it adds up scalars; stored only when the handle has a counter buffer)
-  if (feat || acct) { LAUNCH_STEP(ING, FW, 1, 1); return; }
-  if constexpr (FW != arcle::FW_GENERIC) {  // (generic widths have no compile-time-flag twin: one instantiation less per ingress form)
-    if (p.flags == (uint32_t)HOT_FLAGS) { LAUNCH_STEP(ING, FW, 0, 0, HOT_FLAGS); return; }
+  if constexpr (DEV_BUILD) {
+    if constexpr (ING == arcle::INGRESS_BBOX && FW == arcle::FW_FULL)
+      if (std30) return launch_step_kernel<ING, FW, 1, 1>(g, b, st, p), ARCLE_OK;
+    return ARCLE_ERR_CONFIG;
+  } else {
+    if (feat || acct) return launch_step_kernel<ING, FW, 1, 1>(g, b, st, p), ARCLE_OK;
+    if constexpr (FW != arcle::FW_GENERIC) {  // (generic widths have no compile-time-flag twin: one instantiation less per ingress form)
+      if (p.flags == (uint32_t)HOT_FLAGS) return launch_step_kernel<ING, FW, 0, 0, HOT_FLAGS>(g, b, st, p), ARCLE_OK;
+    }
+    return launch_step_kernel<ING, FW, 0, 0>(g, b, st, p), ARCLE_OK;
   }
-  LAUNCH_STEP(ING, FW, 0, 0);
 }
 template <int ING>
 static int launch_step_ing(int fw, bool acct, bool feat, dim3 g, dim3 b, hipStream_t st, const StepParams& p) {
-  if (fw == arcle::FW_FULL) launch_step_tbl<ING, arcle::FW_FULL>(acct, feat, g, b, st, p);
-  else if (fw == arcle::FW_FAST) launch_step_tbl<ING, arcle::FW_FAST>(acct, feat, g, b, st, p);
-  else launch_step_tbl<ING, arcle::FW_GENERIC>(acct, feat, g, b, st, p);
-  return ARCLE_OK;
-}
-#endif
-
-// which (ingress, flag set) combinations have a self-ordering instantiation (30 x 30, FW_FULL, no accounting)
-static bool grouped_instantiation(int ingress, const StepParams& p) {
-#ifdef ARCLE_FAST_BUILD
-  return ingress == arcle::INGRESS_BBOX && p.flags == (uint32_t)HOT_FLAGS;
-#else
-  const bool tuple5 = ingress == arcle::INGRESS_BBOX || ingress == arcle::INGRESS_BBOX5;
-  if (p.flags == (uint32_t)HOT_FLAGS) return true;  // (tuples, records, int8 and bit-packed masks)
-  if (p.flags == (uint32_t)ARCLE_STEP_ELIDE_SELECTED) return tuple5 || ingress == arcle::INGRESS_POINT;  // (ARCVecEnv without autoreset)
-  if (p.flags == (uint32_t)HOT_PACK_FLAGS) return tuple5;
-  return tuple5 && research_shape(p, ARCLE_STEP_ROWS_INCREMENTAL);
-#endif
+  if (fw == arcle::FW_FULL) return launch_step_tbl<ING, arcle::FW_FULL>(acct, feat, g, b, st, p);
+  if (fw == arcle::FW_FAST) return launch_step_tbl<ING, arcle::FW_FAST>(acct, feat, g, b, st, p);
+  return launch_step_tbl<ING, arcle::FW_GENERIC>(acct, feat, g, b, st, p);
 }
 
 // ... and whether a launch of this handle with these parameters (flags, row shape already filled in) CAN take it (whether it does: plan_launch)
 static bool grouped_applies(const arcle_env* e, int ingress, const StepParams& p) {
   return e->group_enabled && e->order_enabled && p.H == 30 && p.W == 30 && p.PS == ARCLE_MAX_CELLS && !e->d_acct && e->base.long_mask != 0 &&
-         (p.n_envs % (8 * ARCLE_GROUP_SIZE)) == 0 && p.n_envs >= 16 * ARCLE_GROUP_SIZE && grouped_instantiation(ingress, p);
+         (p.n_envs % (8 * ARCLE_GROUP_SIZE)) == 0 && p.n_envs >= 16 * ARCLE_GROUP_SIZE && lean_twin(TW_GROUPED, ingress, p);
 }
 
 // A self-ordering launch reads the actions of 32 envs per wave: fine from device memory (one wave's request serves the whole group out of
@@ -1128,10 +1123,9 @@ static int launch_wpw(const arcle_env* e) {
 static LaunchPlan plan_launch(const arcle_env* e, int ingress, const StepParams& p, bool device_payload) {
   const uint32_t flags = p.flags;
   const bool std30 = p.H == 30 && p.W == 30 && p.PS == ARCLE_MAX_CELLS;
-  const bool tuple5 = ingress == arcle::INGRESS_BBOX || ingress == arcle::INGRESS_BBOX5;
   // which choices exist for this launch at all
   const bool can_group = device_payload && !e->pf_active && grouped_applies(e, ingress, p);
-  const bool any_policy = std30 && flags == (uint32_t)HOT_FLAGS && tuple5;                      // the lean streaming instantiations
+  const bool any_policy = std30 && lean_twin(TW_STREAM, ingress, p);                            // the lean streaming instantiations
   const bool policy_a = !std30 && !(flags & ARCLE_STEP_FEATURE_FLAGS) && ingress != arcle::INGRESS_MASK;  // other shapes: the run-time request
   LaunchPlan pl;
   if (e->forced) {  // (arcle_autotune timing a candidate)
@@ -1476,9 +1470,11 @@ extern "C" int arcle_step_many(arcle_env* e, int ingress, int32_t n_steps, const
   // workgroups of launch t-1 filled from pinned host memory while that launch ran; only step 0 reads across PCIe itself.
   bool prefetch = false;
   // (only where the lean instantiation that carries the copy workgroups applies: the standard 30 x 30 batch with ARCVecEnv's flags)
-  const bool pf_kernel = !e->big && width_class(e->base) == arcle::FW_FULL && e->base.H == 30 && e->base.W == 30 && flags == (uint32_t)HOT_FLAGS &&
-                         !e->d_acct && launch_wpw(e) == WAVES_PER_WG;
-  if (pf_kernel && ingress == arcle::INGRESS_BBOX5 && n_steps > 1 && (n & 3) == 0 && sel) {
+  StepParams pf = e->base;
+  pf.flags = flags;
+  const bool pf_kernel = !e->big && width_class(e->base) == arcle::FW_FULL && e->base.H == 30 && e->base.W == 30 && !e->d_acct &&
+                         launch_wpw(e) == WAVES_PER_WG && lean_twin(TW_PF, ingress, pf);
+  if (pf_kernel && n_steps > 1 && (n & 3) == 0 && sel) {
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, sel) == hipSuccess && attr.type == hipMemoryTypeHost) prefetch = true;
     else (void)hipGetLastError();
@@ -1554,39 +1550,24 @@ extern "C" int arcle_pack_mask_bits(arcle_env* e, const int8_t* sel, uint8_t* bi
   return ARCLE_OK;
 }
 
-#ifdef ARCLE_FAST_BUILD
-template <int ING>
-static int launch_rollout_ing(int fw, dim3 g, dim3 b, hipStream_t st, const StepParams& p) {  // (development builds: the 30 x 30 bbox rollouts only)
-  if (ING != arcle::INGRESS_BBOX || fw == arcle::FW_GENERIC || p.H != 30 || p.W != 30) return ARCLE_ERR_CONFIG;
-  if (p.flags == (uint32_t)HOT_FLAGS) hipLaunchKernelGGL((arcle_rollout_kernel<arcle::INGRESS_BBOX, arcle::FW_FAST, 30, HOT_FLAGS>), g, b, 0, st, p);
-  else if (p.flags == (uint32_t)HOT_PACK_FLAGS) hipLaunchKernelGGL((arcle_rollout_kernel<arcle::INGRESS_BBOX, arcle::FW_FAST, 30, HOT_PACK_FLAGS>), g, b, 0, st, p);
-  else hipLaunchKernelGGL((arcle_rollout_kernel<arcle::INGRESS_BBOX, arcle::FW_FAST, 30>), g, b, 0, st, p);
-  return ARCLE_OK;
-}
-#else
-template <int ING, int FW>
-static void launch_rollout_tbl(dim3 g, dim3 b, hipStream_t st, const StepParams& p) {
-  hipLaunchKernelGGL((arcle_rollout_kernel<ING, FW>), g, b, 0, st, p);
-}
 template <int ING>
 static int launch_rollout_ing(int fw, dim3 g, dim3 b, hipStream_t st, const StepParams& p) {
   // (the rollout keeps planes in registers: lane predication does not matter, FW_FULL shares FW_FAST's code)
-  if constexpr (ING == arcle::INGRESS_BBOX || ING == arcle::INGRESS_POINT) {  // the front-ends' flag sets: compile-time constants of lean instantiations
-    if (fw != arcle::FW_GENERIC && p.H == 30 && p.W == 30 && p.flags == (uint32_t)HOT_FLAGS) {
-      hipLaunchKernelGGL((arcle_rollout_kernel<ING, arcle::FW_FAST, 30, HOT_FLAGS>), g, b, 0, st, p);
-      return ARCLE_OK;
-    }
-    if (fw != arcle::FW_GENERIC && p.H == 30 && p.W == 30 && p.flags == (uint32_t)HOT_PACK_FLAGS) {
-      hipLaunchKernelGGL((arcle_rollout_kernel<ING, arcle::FW_FAST, 30, HOT_PACK_FLAGS>), g, b, 0, st, p);
-      return ARCLE_OK;
-    }
-  }
-  if (fw != arcle::FW_GENERIC && p.H == 30 && p.W == 30) hipLaunchKernelGGL((arcle_rollout_kernel<ING, arcle::FW_FAST, 30>), g, b, 0, st, p);
-  else if (fw != arcle::FW_GENERIC) launch_rollout_tbl<ING, arcle::FW_FAST>(g, b, st, p);
-  else launch_rollout_tbl<ING, arcle::FW_GENERIC>(g, b, st, p);
+  if (fw != arcle::FW_GENERIC && p.H == 30 && p.W == 30 && each_lean([&](auto row) {
+        constexpr int R = decltype(row)::value, FL = LEAN[R].fl;
+        if constexpr (lean_has(R, TW_ROLLOUT, ING)) {
+          if (FL >= 0 && p.flags != (uint32_t)FL) return false;
+          hipLaunchKernelGGL((arcle_rollout_kernel<ING, arcle::FW_FAST, 30, FL>), g, b, 0, st, p);
+          return true;
+        }
+        return false;
+      }))
+    return ARCLE_OK;
+  if constexpr (DEV_BUILD) return ARCLE_ERR_CONFIG;
+  else if (fw != arcle::FW_GENERIC) hipLaunchKernelGGL((arcle_rollout_kernel<ING, arcle::FW_FAST>), g, b, 0, st, p);
+  else hipLaunchKernelGGL((arcle_rollout_kernel<ING, arcle::FW_GENERIC>), g, b, 0, st, p);
   return ARCLE_OK;
 }
-#endif
 
 static int launch_rollout(arcle_env* e, int ingress, int32_t n_steps, const void* sel, const int32_t* op, int32_t* reward,
                           uint8_t* term, uint32_t flags, void* stream) {

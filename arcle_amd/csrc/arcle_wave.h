@@ -1854,12 +1854,10 @@ ARCLE_DEV void wave_step(Wave& w, int env, StepInputs& in, uint64_t t_entry = 0,
 #ifdef ARCLE_TRACE_WAVES  // diagnostic build: per-wave shader clocks into the acct buffer (as uint64[N][8])
   const uint64_t t_in = xl::clock();
 #endif
-#ifndef ARCLE_NO_TOV
   if (is_tuple(ING)) {  // the tuple's arithmetic (sort, clip, rectangle masks, shift distances) runs on the vector ALUs: xl::tov
 #pragma unroll
     for (int i = 0; i < 4; i++) in.payload[i] = xl::tov(in.payload[i]);
   }
-#endif
   Rec r;
   r.w[0] = in.rec[0];
   r.w[1] = in.rec[1];
