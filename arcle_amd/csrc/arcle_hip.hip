@@ -1578,6 +1578,8 @@ static int launch_rollout(arcle_env* e, int ingress, int32_t n_steps, const void
     return fail(e, ARCLE_ERR_ARG, "flag not supported by the rollout kernels");
   if ((flags & (ARCLE_STEP_CONTINUE_RULE | ARCLE_STEP_RESET_ON_SUBMIT)) && ingress != arcle::INGRESS_MASK)
     return fail(e, ARCLE_ERR_CONFIG, "the rollout kernels take ARCLE_STEP_CONTINUE_RULE / _RESET_ON_SUBMIT with mask ingress only");
+  if ((flags & ARCLE_STEP_CONTINUE_RULE) && !e->bufs.plane[ARCLE_PL_SELECTED])  // (as launch_step: the rule compares with `selected`)
+    return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_CONTINUE_RULE needs mask ingress and the `selected` plane");
   if ((flags & ARCLE_STEP_PACK_OBS) && !e->pack_out)
     return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_PACK_OBS without arcle_set_packed_output (rollouts: uint8 [n_steps][n_envs][arcle_packed_obs_size()])");
   if (e->big) {

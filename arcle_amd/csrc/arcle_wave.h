@@ -2360,9 +2360,9 @@ ARCLE_DEV void pack_row(const Wave& w, const Rec& r, uint32_t reward, uint32_t t
   const int P = w.p.P, lane = w.lane;
   if (16 * lane >= stride) return;
   U4 v = have_grid ? grid : w.load(ARCLE_PL_GRID);  // (bytes >= P of the plane row are zero padding)
+  // the 7 metadata bytes as one little-endian word: grid_dim (2), reward int32 (4), terminated (1)
+  const uint64_t meta = (uint64_t)(uint32_t)r.gh() | ((uint64_t)(uint32_t)r.gw() << 8) | ((uint64_t)reward << 16) | ((uint64_t)(term & 0xffu) << 48);
   if (16 * lane + 16 > P) {          // this lane's window holds the metadata bytes
-    // the 7 metadata bytes as one little-endian word: grid_dim (2), reward int32 (4), terminated (1)
-    const uint64_t meta = (uint64_t)(uint32_t)r.gh() | ((uint64_t)(uint32_t)r.gw() << 8) | ((uint64_t)reward << 16) | ((uint64_t)(term & 0xffu) << 48);
 #pragma unroll
     for (int k = 0; k < 16; k++) {
       const int b = 16 * lane + k - P;
@@ -2373,6 +2373,16 @@ ARCLE_DEV void pack_row(const Wave& w, const Rec& r, uint32_t reward, uint32_t t
     }
   }
   *reinterpret_cast<U4*>(out + (size_t)w.env * stride + 16 * lane) = v;
+  // P + 7 > 1024 (P = 1018 ... 1024, e.g. 32 x 32): the row's last 16 bytes lie past the 64 lanes' windows, and lane 0 stores them too
+  if (stride > 16 * 64 && lane == 0) {
+    U4 tail = u4_zero();
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+      const int b = 16 * 64 + k - P;
+      if (b >= 0 && b < 7) tail[k >> 2] |= ((uint32_t)(meta >> (8 * b)) & 0xffu) << (8 * (k & 3));
+    }
+    *reinterpret_cast<U4*>(out + (size_t)w.env * stride + 16 * 64) = tail;
+  }
 }
 ARCLE_DEV void wave_pack_obs(const StepParams& p, WaveLDS* lds, const U2* lut, int env, int lane) {
   Wave w(p, lds, lut, lane, INGRESS_BBOX, FW_GENERIC, false);

@@ -215,18 +215,27 @@ class EmuBackend:
         rc = emu_lib().emu_run(1, ctypes.byref(p))
         assert rc == 0, f"wave emulator reported error {rc}"
 
-    def rollout(self, ingress, payload, op, flags=0):
+    def rollout(self, ingress, payload, op, flags=0, packed=False):
+        """T steps in one emulated launch: payload int32 [T, N, 4 | 2] or (ingress "mask") int8 [T, N, H, W].  packed=True: ARCLE_STEP_PACK_OBS
+        into a [T, N, packed stride] buffer (StepParams.pack_out), returned as a third value."""
         p = self._params()
         T = len(op)
-        pay = np.ascontiguousarray(payload, np.int32)
+        if ingress == "mask":
+            pay = np.ascontiguousarray(np.asarray(payload).astype(np.int8)).reshape(T, self.N, self.P)
+        else:
+            pay = np.ascontiguousarray(payload, np.int32)
         opa = np.ascontiguousarray(op, np.int32)
         reward = np.zeros((T, self.N), np.int32)
         term = np.zeros((T, self.N), np.uint8)
+        if packed:
+            rows = np.full((T, self.N, (self.P + 7 + 15) & ~15), 0x55, np.uint8)
+            p.pack_out = rows.ctypes.data
+            flags |= STEP_PACK_OBS
         p.sel, p.op, p.ingress, p.flags, p.n_steps = pay.ctypes.data, opa.ctypes.data, self.INGRESS[ingress], flags, T
         p.reward, p.term = reward.ctypes.data, term.ctypes.data
         rc = emu_lib().emu_run(3, ctypes.byref(p))
         assert rc == 0, f"wave emulator reported error {rc}"
-        return reward, term
+        return (reward, term, rows) if packed else (reward, term)
 
     def set_task_table(self, inputs, answers):
         T = len(inputs)
@@ -706,11 +715,20 @@ class HipBackend:
             return self.b.plane(field).cpu().numpy().copy()
         return self.b.field(field).cpu().numpy().copy()
 
-    def rollout(self, ingress, payload, op, flags=0):
-        t = self.torch
-        r, tm = self.b.rollout(t.as_tensor(np.ascontiguousarray(payload, np.int32), device=self.b.device),
-                               t.as_tensor(np.ascontiguousarray(op, np.int32), device=self.b.device), flags,
-                               point=(ingress == "point"))
+    def rollout(self, ingress, payload, op, flags=0, packed=False):
+        """EnvBatch.rollout: payload int32 [T, N, 4 | 2] or (ingress "mask", arcle_rollout_mask) int8 [T, N, H, W].  packed=True: every step's
+        packed row (EnvBatch.rollout(packed=)) into a 0x55-filled [T, N, packed_obs_size()] tensor, returned as a third value."""
+        t, dev = self.torch, self.b.device
+        T = len(op)
+        if ingress == "mask":
+            pay = t.as_tensor(np.ascontiguousarray(np.asarray(payload).astype(np.int8)), device=dev).reshape(T, self.N, self.H, self.W)
+        else:
+            pay = t.as_tensor(np.ascontiguousarray(payload, np.int32), device=dev)
+        rows = t.full((T, self.N, self.b.packed_obs_size()), 0x55, dtype=t.uint8, device=dev) if packed else None
+        r, tm = self.b.rollout(pay, t.as_tensor(np.ascontiguousarray(op, np.int32), device=dev), flags,
+                               point=(ingress == "point"), mask=(ingress == "mask"), packed=rows)
+        if packed:
+            return r.cpu().numpy(), tm.cpu().numpy(), rows.cpu().numpy()
         return r.cpu().numpy(), tm.cpu().numpy()
 
     def set_task_table(self, inputs, answers):
@@ -842,6 +860,8 @@ def load_fixture(name):
 
 
 STEP_ELIDE_SELECTED = 2
+STEP_CONTINUE_RULE, STEP_RESET_ON_SUBMIT, STEP_PACK_OBS = 32, 64, 256
+MOVE_ROTATE_FLIP = range(20, 28)  # O2ARCv2Env table slots of Move (4), Rotate (2), Flip (2): what the continuation rule applies to
 
 
 def can_elide(ops):
@@ -896,6 +916,61 @@ def replay_fixture(backend_cls, name, max_steps=None, flags=0):
 
 
 # ---- random differential traces (no reference needed: backend vs oracle) ---------------------------------
+def random_payload(rng, ing, N, H, W, int8_masks=False, bad_tuples=False):
+    """One step's actions of N envs in ingress form `ing` ("bbox" int32 [N, 4], "point" int32 [N, 2], "mask" int8 [N, H, W]).
+    Masks are 0 / 1 (empty, sparse noise, one cell, a small block) or, int8_masks=True, arbitrary int8 values (see
+    random_trace_compare).  bad_tuples: about one env in eight gets a tuple outside the wrappers' action space (negative
+    coordinates, a point past the plane, a bbox corner past it): ARCLE_ST_BAD_SELECTION where the reference would raise."""
+    if ing == "mask" and int8_masks:
+        pay = np.zeros((N, H, W), np.int8)
+        for n in range(N):
+            t = rng.integers(0, 6)
+            x, y = rng.integers(0, H), rng.integers(0, W)
+            if t == 1:
+                pay[n] = rng.integers(-3, 4, (H, W)) * (rng.random((H, W)) < rng.random() * 0.1)
+            elif t == 2:
+                pay[n, x, y] = [1, 2, -1, 127, -128][rng.integers(0, 5)]
+            elif t == 3:
+                pay[n, x, y] = 2
+                pay[n, rng.integers(0, H), rng.integers(0, W)] -= 1
+            elif t == 4:
+                pay[n] = rng.random((H, W)) < rng.random() * 0.3
+                pay[n][rng.random((H, W)) < 0.01] = -1
+            elif t == 5:
+                pay[n, x:x + rng.integers(1, 6), y:y + rng.integers(1, 6)] = 1
+                pay[n, x, y] = 5
+    elif ing == "bbox":
+        pay = np.stack([rng.integers(0, H, N), rng.integers(0, W, N), rng.integers(0, H, N), rng.integers(0, W, N)], 1)
+        small = rng.random(N) < 0.5
+        pay[small, 2] = np.minimum(H - 1, pay[small, 0] + rng.integers(0, 4, small.sum()))
+        pay[small, 3] = np.minimum(W - 1, pay[small, 1] + rng.integers(0, 4, small.sum()))
+    elif ing == "point":
+        pay = np.stack([rng.integers(0, H, N), rng.integers(0, W, N)], 1)
+    else:
+        pay = np.zeros((N, H, W), np.int8)
+        for n in range(N):
+            t = rng.integers(0, 4)
+            if t == 1:
+                pay[n] = rng.random((H, W)) < rng.random() * 0.3
+            elif t == 2:
+                x, y = rng.integers(0, H), rng.integers(0, W)
+                pay[n, x, y] = 1
+            elif t == 3:
+                x, y = rng.integers(0, H), rng.integers(0, W)
+                pay[n, x:x + rng.integers(1, 5), y:y + rng.integers(1, 5)] = 1
+    if bad_tuples and ing != "mask":
+        bad = np.nonzero(rng.random(N) < 0.125)[0]
+        for n in bad:
+            k = rng.integers(0, 3)
+            if k == 0:
+                pay[n, rng.integers(0, 2)] = -rng.integers(1, 40)
+            elif k == 1:
+                pay[n, 0], pay[n, 1] = H + rng.integers(0, 3), W + rng.integers(0, 3)
+            else:
+                pay[n, rng.integers(0, pay.shape[1])] = [-1, -128, 1 << 20, -(1 << 31)][rng.integers(0, 4)]
+    return pay
+
+
 def random_trace_compare(backend_cls, kind, ops, H, W, N, S, seed, max_trial=-1, flags=0, op_weights=None,
                          bad_ops=False, new_forms=False, int8_masks=False):
     """Steps `backend_cls` and the oracle side by side on seeded random tasks/actions; returns mismatches.
@@ -939,43 +1014,7 @@ def random_trace_compare(backend_cls, kind, ops, H, W, N, S, seed, max_trial=-1,
         if bad_ops and s % 7 == 3:
             op[rng.integers(0, N)] = n_ops + rng.integers(0, 3)
         ing = "mask" if int8_masks else ["bbox", "bbox", "point", "mask"][rng.integers(0, 4)]
-        if int8_masks:
-            pay = np.zeros((N, H, W), np.int8)
-            for n in range(N):
-                t = rng.integers(0, 6)
-                x, y = rng.integers(0, H), rng.integers(0, W)
-                if t == 1:
-                    pay[n] = rng.integers(-3, 4, (H, W)) * (rng.random((H, W)) < rng.random() * 0.1)
-                elif t == 2:
-                    pay[n, x, y] = [1, 2, -1, 127, -128][rng.integers(0, 5)]
-                elif t == 3:
-                    pay[n, x, y] = 2
-                    pay[n, rng.integers(0, H), rng.integers(0, W)] -= 1
-                elif t == 4:
-                    pay[n] = rng.random((H, W)) < rng.random() * 0.3
-                    pay[n][rng.random((H, W)) < 0.01] = -1
-                elif t == 5:
-                    pay[n, x:x + rng.integers(1, 6), y:y + rng.integers(1, 6)] = 1
-                    pay[n, x, y] = 5
-        elif ing == "bbox":
-            pay = np.stack([rng.integers(0, H, N), rng.integers(0, W, N), rng.integers(0, H, N), rng.integers(0, W, N)], 1)
-            small = rng.random(N) < 0.5
-            pay[small, 2] = np.minimum(H - 1, pay[small, 0] + rng.integers(0, 4, small.sum()))
-            pay[small, 3] = np.minimum(W - 1, pay[small, 1] + rng.integers(0, 4, small.sum()))
-        elif ing == "point":
-            pay = np.stack([rng.integers(0, H, N), rng.integers(0, W, N)], 1)
-        else:
-            pay = np.zeros((N, H, W), np.int8)
-            for n in range(N):
-                t = rng.integers(0, 4)
-                if t == 1:
-                    pay[n] = rng.random((H, W)) < rng.random() * 0.3
-                elif t == 2:
-                    x, y = rng.integers(0, H), rng.integers(0, W)
-                    pay[n, x, y] = 1
-                elif t == 3:
-                    x, y = rng.integers(0, H), rng.integers(0, W)
-                    pay[n, x:x + rng.integers(1, 5), y:y + rng.integers(1, 5)] = 1
+        pay = random_payload(rng, ing, N, H, W, int8_masks)
         if new_forms and ing == "bbox":
             r1, t1 = be.step("bbox5", np.concatenate([pay, op[:, None]], 1), None, flags)
         elif new_forms and ing == "mask":
@@ -1050,31 +1089,59 @@ def task_table_compare(backend_cls, H, W, N, T, seed):
     return errs
 
 
-def rollout_compare(backend_cls, kind, ops, H, W, N, T, seed, ingress="bbox", flags=0, max_trial=3):
-    """One T-step rollout launch vs T sequential oracle steps: per-step reward/terminated, final state, counters."""
-    rng = np.random.default_rng(seed)
-    be = backend_cls(N, H, W, max_trial, kind, ops)
-    orc = OracleBackend(N, H, W, max_trial, kind, ops)
+def unpack_rows(rows, H, W):
+    """Packed observation rows (uint8 [..., R]: grid | grid_dim | reward int32 LE | terminated) -> (grid int8 [M, H, W], grid_dim int8 [M, 2],
+    reward int32 [M], terminated uint8 [M])."""
+    P = H * W
+    rows = np.ascontiguousarray(rows, np.uint8).reshape(-1, np.shape(rows)[-1])
+    return (rows[:, :P].view(np.int8).reshape(-1, H, W), rows[:, P:P + 2].view(np.int8),
+            np.ascontiguousarray(rows[:, P + 2:P + 6]).view("<i4").reshape(-1), rows[:, P + 6])
+
+
+def rollout_tasks(rng, N, H, W):
+    """Seeded tasks of rollout_compare (answer == input: a Submit before any edit terminates, later ones count trials)."""
     inp = np.zeros((N, H, W), np.int8)
     idim = np.zeros((N, 2), np.int8)
     for n in range(N):
         ih, iw = rng.integers(1, H + 1), rng.integers(1, W + 1)
         inp[n, :ih, :iw] = rng.integers(0, 4, (ih, iw))
         idim[n] = (ih, iw)
+    return inp, idim
+
+
+def rollout_actions(rng, ops, ingress, N, H, W, T, op_weights=None, bad_ops=False, int8_masks=False, bad_tuples=False):
+    """(payload [T, N, ...], op int32 [T, N]) of a random T-step rollout: ops uniform or by op_weights, about 5 % Submits, bad_ops: about 2 %
+    op indices outside the table (n_ops, n_ops + 1, 64, -1)."""
+    n_ops = len(ops)
+    if op_weights is None:
+        op = rng.integers(0, n_ops, (T, N)).astype(np.int32)
+    else:
+        w = np.asarray(op_weights, float)
+        op = rng.choice(n_ops, size=(T, N), p=w / w.sum()).astype(np.int32)
+    op[rng.random((T, N)) < 0.05] = n_ops - 1  # some submits (answer == input: terminations, trial counting)
+    if bad_ops:
+        bad = rng.random((T, N)) < 0.02
+        op[bad] = np.array([n_ops, n_ops + 1, 64, -1], np.int32)[rng.integers(0, 4, int(bad.sum()))]
+    pay = np.stack([random_payload(rng, ingress, N, H, W, int8_masks, bad_tuples) for _ in range(T)])
+    return pay.astype(np.int8 if ingress == "mask" else np.int32), op
+
+
+def rollout_compare(backend_cls, kind, ops, H, W, N, T, seed, ingress="bbox", flags=0, max_trial=3, int8_masks=False, op_weights=None,
+                    bad_ops=False, bad_tuples=False, packed=False, actions=None):
+    """One T-step rollout launch vs T sequential oracle steps: per-step reward/terminated, final state, counters, status.
+    ingress "bbox" | "point" | "mask" (0/1 masks, or int8_masks=True arbitrary int8 values); op_weights / bad_ops / bad_tuples: see
+    rollout_actions; packed=True: the launch also writes every step's packed row (ARCLE_STEP_PACK_OBS), each compared with the oracle's
+    grid, grid_dim, reward and terminated after that step.  actions: a caller's (payload, op) instead of the random ones."""
+    rng = np.random.default_rng(seed)
+    be = backend_cls(N, H, W, max_trial, kind, ops)
+    orc = OracleBackend(N, H, W, max_trial, kind, ops)
+    inp, idim = rollout_tasks(rng, N, H, W)
     for b in (be, orc):
         b.set_tasks(inp, idim, inp.copy(), idim.copy())
         b.reset()
-    op = rng.integers(0, len(ops), (T, N)).astype(np.int32)
-    op[rng.random((T, N)) < 0.05] = len(ops) - 1  # some submits (answer == input: terminations, trial counting)
-    if ingress == "bbox":
-        pay = np.stack([rng.integers(0, H, (T, N)), rng.integers(0, W, (T, N)), rng.integers(0, H, (T, N)),
-                        rng.integers(0, W, (T, N))], -1).astype(np.int32)
-        small = rng.random((T, N)) < 0.5
-        pay[..., 2] = np.where(small, np.minimum(H - 1, pay[..., 0] + rng.integers(0, 3, (T, N))), pay[..., 2])
-        pay[..., 3] = np.where(small, np.minimum(W - 1, pay[..., 1] + rng.integers(0, 3, (T, N))), pay[..., 3])
-    else:
-        pay = np.stack([rng.integers(0, H, (T, N)), rng.integers(0, W, (T, N))], -1).astype(np.int32)
-    r1, t1 = be.rollout(ingress, pay, op, flags)
+    pay, op = actions if actions is not None else rollout_actions(rng, ops, ingress, N, H, W, T, op_weights, bad_ops, int8_masks, bad_tuples)
+    out = be.rollout(ingress, pay, op, flags, packed=packed)
+    r1, t1 = out[0], out[1]
     errs = []
     for t in range(T):
         r2, t2 = orc.step(ingress, pay[t], op[t], flags)
@@ -1082,6 +1149,14 @@ def rollout_compare(backend_cls, kind, ops, H, W, N, T, seed, ingress="bbox", fl
             errs.append(f"step {t}: reward differs for envs {np.nonzero(r1[t] != r2)[0].tolist()}")
         if not np.array_equal(t1[t], t2):
             errs.append(f"step {t}: terminated differs for envs {np.nonzero(t1[t] != t2)[0].tolist()}")
+        if packed:
+            g, d, rw, tm = unpack_rows(out[2][t], H, W)
+            for name, got, want in (("grid", g, orc.get("grid")), ("grid_dim", d, orc.get("grid_dim")), ("reward", rw, r2), ("terminated", tm, t2)):
+                bad = np.nonzero((np.asarray(got).reshape(N, -1) != np.asarray(want).reshape(N, -1)).any(1))[0]
+                if len(bad):
+                    errs.append(f"step {t}: packed row {name} differs for envs {bad.tolist()}")
+        if len(errs) > 12:
+            break
     for f in [f for f in PLANES if f in O.KIND_PLANES[kind]] + list(REC):
         if f in ("clip_dim", "object_dim", "object_pos", "active", "rotation_parity") and kind != "o2arc" and not (kind == "arc" and f == "clip_dim"):
             continue
@@ -1089,9 +1164,66 @@ def rollout_compare(backend_cls, kind, ops, H, W, N, T, seed, ingress="bbox", fl
             errs.append(f"final state: field {f} differs")
     if not np.array_equal(be.counters(), orc.counters()):
         errs.append("final counters differ")
-    if be.status() != orc.status():
-        errs.append("status flags differ")
+    s1, s2 = be.status(), orc.status()
+    if s1 != s2:
+        errs.append(f"status flags differ: {s1} vs oracle {s2}")
     return errs
+
+
+def rollout_vs_steps(backend_cls, H, W, N, T, seed, flags, max_trial=3, int8_masks=False, continue_stream=False, packed=False):
+    """A T-step mask rollout vs T single mask steps of a twin of the same backend, for the flags the oracle does not model
+    (ARCLE_STEP_CONTINUE_RULE, _RESET_ON_SUBMIT): per-step reward / terminated (packed=True: and every step's packed row vs the twin's
+    grid / grid_dim / reward / terminated after that step), then the final planes, record, counters and status.  O2ARCv2Env table.
+    continue_stream: about 40 % of the envs per step send the twin's current `selected` plane (when not empty) with a Move / Rotate /
+    Flip, so the continuation branch of the rule is taken (random masks almost never equal the plane), and 40 % of the envs with an
+    empty plane lift their random selection with one of those ops.  Returns (errors, hits: continuation candidates sent)."""
+    ops = O.o2arc_ops()
+    rng = np.random.default_rng(seed)
+    be, tw = backend_cls(N, H, W, max_trial, "o2arc", ops), backend_cls(N, H, W, max_trial, "o2arc", ops)
+    inp, idim = rollout_tasks(rng, N, H, W)
+    for b in (be, tw):
+        b.set_tasks(inp, idim, inp.copy(), idim.copy())
+        b.reset()
+    pays, opl, want, hits = [], [], [], 0
+    for t in range(T):
+        pay, op = rollout_actions(rng, ops, "mask", N, H, W, 1, int8_masks=int8_masks)
+        pay, op = pay[0], op[0]
+        if continue_stream:
+            sel = tw.get("selected")
+            live = sel.reshape(N, -1).any(1)
+            hit = (rng.random(N) < 0.4) & live
+            pay[hit] = sel[hit]
+            lift = ((rng.random(N) < 0.4) & ~live) | hit  # (an object op on an empty `selected` lifts the new selection)
+            op[lift] = rng.integers(MOVE_ROTATE_FLIP.start, MOVE_ROTATE_FLIP.stop, int(lift.sum()))
+            hits += int(hit.sum())
+        r, tm = tw.step("mask", pay, op, flags)
+        pays.append(pay)
+        opl.append(op)
+        want.append((r, tm, tw.get("grid"), tw.get("grid_dim")))
+    out = be.rollout("mask", np.stack(pays), np.stack(opl), flags, packed=packed)
+    errs = []
+    for t, (r, tm, g, d) in enumerate(want):
+        if not np.array_equal(out[0][t], r):
+            errs.append(f"step {t}: reward differs for envs {np.nonzero(out[0][t] != r)[0].tolist()}")
+        if not np.array_equal(out[1][t], tm):
+            errs.append(f"step {t}: terminated differs for envs {np.nonzero(out[1][t] != tm)[0].tolist()}")
+        if packed:
+            pg, pd, pr, pt = unpack_rows(out[2][t], H, W)
+            for name, a, b in (("grid", pg, g), ("grid_dim", pd, d), ("reward", pr, r), ("terminated", pt, tm)):
+                bad = np.nonzero((np.asarray(a).reshape(N, -1) != np.asarray(b).reshape(N, -1)).any(1))[0]
+                if len(bad):
+                    errs.append(f"step {t}: packed row {name} differs for envs {bad.tolist()}")
+        if len(errs) > 12:
+            break
+    for f in PLANES + list(REC):
+        if not np.array_equal(be.get(f), tw.get(f)):
+            errs.append(f"final state: field {f} differs")
+    if not np.array_equal(be.counters(), tw.counters()):
+        errs.append("final counters differ")
+    s1, s2 = be.status(), tw.status()
+    if s1 != s2:
+        errs.append(f"status flags differ: {s1} vs single steps {s2}")
+    return errs, hits
 
 
 def spiral_grid(H, W):

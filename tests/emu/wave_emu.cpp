@@ -162,6 +162,7 @@ const size_t STACK = 256 * 1024;
   } while (0)
 #define RUN_TRANS(I, F) arcle::wave_transition_row<I, F>(*g_p, &g_lds.wave[0], g_lds.lut, g_env, lane)
 #define RUN_ROLL(I, F) arcle::wave_rollout<I, F>(*g_p, &g_lds.wave[0], g_lds.lut, g_env, lane)
+#define RUN_ROLL_LEAN(I, FL) arcle::wave_rollout<I, arcle::FW_FAST, FL>(*g_p, &g_lds.wave[0], g_lds.lut, g_env, lane)
 
 // the same width classes the HIP library launches: FW_FULL when 16 <= W <= 32 and the plane stride is 1024
 int width_class() {
@@ -218,7 +219,16 @@ void lane_main(int lane) {
     arcle::wave_reset_table(*g_p, &g_lds.wave[0], g_lds.lut, g_env, lane);
   else if (g_kind == 3) {
     const int f = fw ? 1 : 0;  // (the library launches FW_FAST rollouts for FW_FULL too)
-    switch (g_p->ingress * 2 + f) {
+    // as launch_rollout_ing (arcle_hip.hip): at 30 x 30, bbox / point rollouts with a lean flag set (AUTORESET | ELIDE_SELECTED, the same
+    // plus PACK_OBS) run the twin whose flag set is a compile-time constant; every other rollout runs FL = -1
+    constexpr int hot = ARCLE_STEP_AUTORESET | ARCLE_STEP_ELIDE_SELECTED;
+    const int lean = (f && g_p->H == 30 && g_p->W == 30 && (g_p->ingress == 1 || g_p->ingress == 2))
+                         ? (g_p->flags == (uint32_t)hot ? 1 : g_p->flags == (uint32_t)(hot | ARCLE_STEP_PACK_OBS) ? 2 : 0) : 0;
+    switch (lean ? 100 + 2 * g_p->ingress + lean : g_p->ingress * 2 + f) {
+      case 103: RUN_ROLL_LEAN(1, hot); break;
+      case 104: RUN_ROLL_LEAN(1, hot | ARCLE_STEP_PACK_OBS); break;
+      case 105: RUN_ROLL_LEAN(2, hot); break;
+      case 106: RUN_ROLL_LEAN(2, hot | ARCLE_STEP_PACK_OBS); break;
       case 0: RUN_ROLL(0, 0); break;
       case 1: RUN_ROLL(0, 1); break;
       case 2: RUN_ROLL(1, 0); break;

@@ -71,6 +71,38 @@ def test_emulated_rollout_other_kinds():
         assert not errs, "\n".join(errs[:10])
 
 
+@pytest.mark.parametrize("H,W", [(30, 30), (16, 24), (5, 7), (32, 32), (31, 33)])
+def test_emulated_mask_rollout_vs_oracle(H, W):
+    """wave_rollout with mask ingress (arcle_rollout_mask) at a 30 x 30, a FW_FAST and a FW_GENERIC shape: flags 0-3, 0/1 or arbitrary
+    int8 masks, out-of-range ops; per-step reward / terminated, every step's packed row (odd flags) and the final state vs the oracle.
+    32 x 32 and 31 x 33 (P + 7 > 1024): the packed row's metadata lies past the 64 lanes' windows."""
+    for flags in (0, O.STEP_AUTORESET, B.STEP_ELIDE_SELECTED, O.STEP_AUTORESET | B.STEP_ELIDE_SELECTED):
+        errs = B.rollout_compare(B.EmuBackend, "o2arc", O.o2arc_ops(), H, W, N=6, T=40, seed=H * 7 + W + flags, ingress="mask", flags=flags,
+                                 int8_masks=bool(flags & 1), op_weights=OBJ_HEAVY, bad_ops=True, packed=bool(flags & 1))
+        assert not errs, f"flags {flags}:\n" + "\n".join(errs[:10])
+
+
+@pytest.mark.parametrize("ingress", ["bbox", "point"])
+def test_emulated_lean_rollout_twins(ingress):
+    """At 30 x 30 with AUTORESET | ELIDE_SELECTED (+ PACK_OBS) the emulator runs the rollout twin whose flag set is a compile-time
+    constant, as launch_rollout_ing does; out-of-range tuples and ops compare ARCLE_ST_BAD_SELECTION / _BAD_OP too."""
+    for flags in (3, 3 | B.STEP_PACK_OBS):
+        errs = B.rollout_compare(B.EmuBackend, "o2arc", O.o2arc_ops(), 30, 30, N=6, T=40, seed=flags, ingress=ingress, flags=flags & 3,
+                                 op_weights=OBJ_HEAVY, bad_ops=True, bad_tuples=True, packed=bool(flags & B.STEP_PACK_OBS))
+        assert not errs, f"flags {flags}:\n" + "\n".join(errs[:10])
+
+
+@pytest.mark.parametrize("H,W", [(10, 10), (16, 24)])
+@pytest.mark.parametrize("flags", [B.STEP_CONTINUE_RULE, B.STEP_RESET_ON_SUBMIT, B.STEP_CONTINUE_RULE | B.STEP_RESET_ON_SUBMIT])
+def test_emulated_mask_rollout_trace_flags(H, W, flags):
+    """The rollout takes CONTINUE_RULE / RESET_ON_SUBMIT (mask ingress only): equal to the same steps taken singly, on a stream whose
+    logged selections equal the current `selected` plane before a Move / Rotate / Flip (the continuation branch)."""
+    errs, hits = B.rollout_vs_steps(B.EmuBackend, H, W, N=6, T=40, seed=flags + H, flags=flags, int8_masks=(H == 10),
+                                    continue_stream=True, packed=True)
+    assert not errs, "\n".join(errs[:10])
+    assert hits >= 10, hits
+
+
 @pytest.mark.parametrize("H,W", [(30, 30), (32, 32), (17, 21), (12, 12), (6, 40)])
 def test_emulated_floodfill_worst_case(H, W):
     errs = B.floodfill_worst_case_compare(B.EmuBackend, H, W)
