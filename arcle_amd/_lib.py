@@ -16,7 +16,7 @@ UNITS = [os.path.join(_CSRC, "arcle_hip.hip"), os.path.join(_CSRC, "arcle_big.hi
 SOURCES = UNITS + [os.path.join(_CSRC, "arcle_wave.h"), os.path.join(_CSRC, "arcle_big.h"), os.path.join(_CSRC, "arcle_big_params.h"),
                    os.path.join(_CSRC, "..", "..", "include", "arcle_hip.h")]
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 N_PLANES = 8
 MAX_OPS = 64
 BITS_STRIDE = 128  # bytes between envs of a bit-packed mask array (ARCLE_MAX_CELLS / 8)
@@ -24,7 +24,7 @@ INGRESS = {"mask": 0, "bbox": 1, "point": 2, "bbox5": 3, "bits": 4}  # enum arcl
 EXPORTS = ["arcle_abi_version", "arcle_create", "arcle_destroy", "arcle_get_buffers", "arcle_set_op_table",
            "arcle_can_elide_selected", "arcle_reset", "arcle_set_task_table", "arcle_reset_from_table",
            "arcle_step_mask", "arcle_step_bbox", "arcle_step_point", "arcle_step_bbox5", "arcle_step_bits", "arcle_pack_mask_bits", "arcle_mask_bits_stride",
-           "arcle_step_many", "arcle_set_dispatch_order", "arcle_hint_next_ops", "arcle_launch_info", "arcle_autotune", "arcle_rollout_bbox", "arcle_rollout_point", "arcle_rollout_mask", "arcle_set_truncation",
+           "arcle_step_many", "arcle_set_dispatch_order", "arcle_hint_next_ops", "arcle_launch_info", "arcle_autotune", "arcle_rollout_bbox", "arcle_rollout_point", "arcle_rollout_mask", "arcle_rollout_ex", "arcle_set_truncation",
            "arcle_packed_obs_size", "arcle_pack_obs", "arcle_set_packed_output", "arcle_set_sampler", "arcle_reset_sampled",
            "arcle_reset_from_table_aug", "arcle_set_dense_output", "arcle_invalidate", "arcle_flat_obs_size", "arcle_flatten_obs",
            "arcle_set_flat_output", "arcle_set_flat_output_ex", "arcle_set_flat_seq", "arcle_get_state_rows", "arcle_set_state_rows",
@@ -39,6 +39,11 @@ class ArcleHipError(RuntimeError):
 class Config(ctypes.Structure):
     _fields_ = [("n_envs", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
                 ("max_trial", ctypes.c_int32), ("device", ctypes.c_int32), ("plane_stride", ctypes.c_int32)]
+
+
+class RolloutOut(ctypes.Structure):  # arcle_rollout_out
+    _fields_ = [("trunc", ctypes.c_void_p), ("dense", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("rows_stride", ctypes.c_int32),
+                ("rows_filtered", ctypes.c_int32), ("packed", ctypes.c_void_p)]
 
 
 class Buffers(ctypes.Structure):
@@ -133,6 +138,7 @@ def lib():
     L.arcle_set_packed_output.argtypes = [vp, vp]
     for name in ("arcle_rollout_bbox", "arcle_rollout_point", "arcle_rollout_mask"):
         getattr(L, name).argtypes = [vp, i32, vp, vp, vp, vp, u32, vp]
+    L.arcle_rollout_ex.argtypes = [vp, ctypes.c_int, i32, vp, vp, vp, vp, ctypes.POINTER(RolloutOut), u32, vp]
     L.arcle_flat_obs_size.argtypes = [vp, ctypes.c_int]
     L.arcle_flatten_obs.argtypes = [vp, vp, i32, ctypes.c_int, vp]
     L.arcle_set_flat_output.argtypes = [vp, vp, i32, ctypes.c_int]

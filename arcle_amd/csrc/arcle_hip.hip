@@ -456,7 +456,33 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) __attribute__((amdgpu_waves_per_
   xl::wg_barrier();
   const int env = wave_of_launch();
   if (env >= p.n_envs) return;
-  arcle::wave_rollout<ING, FW, FL>(p, &lds.wave[threadIdx.x >> 6], lds.lut, env, (int)(threadIdx.x & 63));
+  arcle::wave_rollout<ING, FW, FL, 0>(p, &lds.wave[threadIdx.x >> 6], lds.lut, env, (int)(threadIdx.x & 63));
+}
+// ... with the research env's step flags and their per-step outputs (arcle_rollout_ex: ARCLE_ROLLOUT_FEAT_FLAGS; a kernel of its own so
+// that the plain rollouts keep their code and their names in the profiles)
+template <int ING, int FW, int WC = 0, int FL = -1>
+__global__ __launch_bounds__(64 * WAVES_PER_WG) __attribute__((amdgpu_waves_per_eu(ARCLE_ROLLOUT_WAVES))) void arcle_rollout_feat_kernel(const StepParams pa) {
+  StepParams p = pa;
+  if (WC == 30) {
+    p.H = p.W = 30;
+    p.P = 900;
+    p.div_magic = 65536u / 30u + 1u;
+    p.nseg = 2;
+  }
+  if (FL >= 0) {  // (as arcle_step_kernel: the flag set and the shape of the rows are compile-time constants; the launcher checked them)
+    p.flags = (uint32_t)FL & 0xffffu;
+    if (FL & ARCLE_STEP_FLAT_OBS) {
+      p.flat_filter = (FL & ARCLE_STEPX_FLAT_FILTERED) ? 1 : 0;
+      p.flat_tail = 0;
+      if (WC == 30) p.flat_stride = (FL & ARCLE_STEPX_FLAT_FILTERED) ? ARCLE_ROW30_FILTERED_STRIDE : ARCLE_ROW30_FULL_STRIDE;
+    }
+  }
+  __shared__ BlockLDS lds;
+  arcle::lut_init(lds.lut, (int)threadIdx.x);
+  xl::wg_barrier();
+  const int env = wave_of_launch();
+  if (env >= p.n_envs) return;
+  arcle::wave_rollout<ING, FW, FL, 1>(p, &lds.wave[threadIdx.x >> 6], lds.lut, env, (int)(threadIdx.x & 63));
 }
 
 __global__ __launch_bounds__(64 * WAVES_PER_WG) void arcle_flatten_kernel(const StepParams p) {
@@ -942,7 +968,7 @@ static constexpr int RESEARCH_INC_FL = RESEARCH_FL | ARCLE_STEP_ROWS_INCREMENTAL
 //   grouped   ... FL | ARCLE_STEPX_GROUPED: the launch orders itself (p.group_magic, see plan_launch)
 //   stream    ... FL | ARCLE_STEPX_STREAM | stream_bits(policy), one per policy 'A' 'B' 'H' 'J': the grid plane requested beside the scalars
 //   prefetch  <INGRESS_BBOX5_PF, ...>: the next step's records copied from host memory by the front workgroups (arcle_step_many)
-//   rollout   arcle_rollout_kernel<ING, FW_FAST, 30, FL>
+//   rollout   arcle_rollout_kernel<ING, FW_FAST, 30, FL>; rows with FEAT 1: arcle_rollout_feat_kernel<ING, FW_FAST, 30, FL> (arcle_rollout_ex)
 // A launch takes the first row that matches its flags (-1: a step without feature flags, any rollout) and has a twin that applies, in the
 // order prefetch, grouped, stream, plain.  The flag sets are distinct and -1 comes last, so the lookups of plan_launch (lean_twin) agree.
 // Development builds (-DARCLE_FAST_BUILD: seconds instead of minutes) keep the cells marked DEV, for bbox tuples only, and of the kernels
@@ -965,7 +991,7 @@ static constexpr LeanRow LEAN[] = {
     {HOT_FLAGS,                  0, {I_ANY | DEV,   I_ANY | DEV,     I_T5 | DEV,     I_BBOX5,  I_BBOX | I_POINT | DEV}},
     {ARCLE_STEP_ELIDE_SELECTED,  0, {0,             I_T5 | I_POINT,  0,              0,        0}},  // (ARCVecEnv without the auto-reset)
     {HOT_PACK_FLAGS,             0, {I_ANY,         I_T5,            0,              0,        I_BBOX | I_POINT | DEV}},
-    {RESEARCH_FL,                1, {I_ANY | DEV,   0,               0,              0,        0}},
+    {RESEARCH_FL,                1, {I_ANY | DEV,   0,               0,              0,        I_BBOX | I_POINT | DEV}},
     {RESEARCH_INC_FL,            1, {I_ANY | DEV,   I_T5,            0,              0,        0}},
     {-1,                         0, {I_ANY | DEV,   0,               0,              0,        I_MASK | I_BBOX | I_POINT | DEV}},
 };
@@ -1553,17 +1579,26 @@ extern "C" int arcle_pack_mask_bits(arcle_env* e, const int8_t* sel, uint8_t* bi
 template <int ING>
 static int launch_rollout_ing(int fw, dim3 g, dim3 b, hipStream_t st, const StepParams& p) {
   // (the rollout keeps planes in registers: lane predication does not matter, FW_FULL shares FW_FAST's code)
+  // feat: the research flags (arcle_rollout_ex) — the FEAT 1 rows of the table and arcle_rollout_feat_kernel; the others never take them
+  const bool feat = (p.flags & ARCLE_ROLLOUT_FEAT_FLAGS) != 0u;
   if (fw != arcle::FW_GENERIC && p.H == 30 && p.W == 30 && each_lean([&](auto row) {
         constexpr int R = decltype(row)::value, FL = LEAN[R].fl;
         if constexpr (lean_has(R, TW_ROLLOUT, ING)) {
-          if (FL >= 0 && p.flags != (uint32_t)FL) return false;
-          hipLaunchKernelGGL((arcle_rollout_kernel<ING, arcle::FW_FAST, 30, FL>), g, b, 0, st, p);
+          if constexpr (LEAN[R].feat) {
+            if (!feat || !lean_match(FL, p)) return false;
+            hipLaunchKernelGGL((arcle_rollout_feat_kernel<ING, arcle::FW_FAST, 30, FL>), g, b, 0, st, p);
+          } else {
+            if (feat || (FL >= 0 && p.flags != (uint32_t)FL)) return false;
+            hipLaunchKernelGGL((arcle_rollout_kernel<ING, arcle::FW_FAST, 30, FL>), g, b, 0, st, p);
+          }
           return true;
         }
         return false;
       }))
     return ARCLE_OK;
   if constexpr (DEV_BUILD) return ARCLE_ERR_CONFIG;
+  else if (feat && fw != arcle::FW_GENERIC) hipLaunchKernelGGL((arcle_rollout_feat_kernel<ING, arcle::FW_FAST>), g, b, 0, st, p);
+  else if (feat) hipLaunchKernelGGL((arcle_rollout_feat_kernel<ING, arcle::FW_GENERIC>), g, b, 0, st, p);
   else if (fw != arcle::FW_GENERIC) hipLaunchKernelGGL((arcle_rollout_kernel<ING, arcle::FW_FAST>), g, b, 0, st, p);
   else hipLaunchKernelGGL((arcle_rollout_kernel<ING, arcle::FW_GENERIC>), g, b, 0, st, p);
   return ARCLE_OK;
@@ -1631,6 +1666,108 @@ extern "C" int arcle_rollout_point(arcle_env* e, int32_t n_steps, const int32_t*
 extern "C" int arcle_rollout_mask(arcle_env* e, int32_t n_steps, const int8_t* sel, const int32_t* op, int32_t* reward,
                                   uint8_t* term, uint32_t flags, void* stream) {
   return launch_rollout(e, arcle::INGRESS_MASK, n_steps, sel, op, reward, term, flags, stream);
+}
+
+// ABI 6: a rollout with the research env's step flags and every step's outputs (include/arcle_hip.h).  Everything is checked before
+// anything is enqueued: a refused call writes nothing.
+extern "C" int arcle_rollout_ex(arcle_env* e, int ingress, int32_t n_steps, const void* sel, const int32_t* op, int32_t* reward,
+                                uint8_t* term, const arcle_rollout_out* out, uint32_t flags, void* stream) {
+  if (!e || !sel || !op || !reward || !term) return ARCLE_ERR_ARG;
+  if (ingress != arcle::INGRESS_BBOX && ingress != arcle::INGRESS_POINT && ingress != arcle::INGRESS_MASK)
+    return fail(e, ARCLE_ERR_ARG, "arcle_rollout_ex: ingress ARCLE_INGRESS_BBOX, _POINT or _MASK");
+  if (n_steps <= 0) return fail(e, ARCLE_ERR_ARG, "n_steps must be positive");
+  if (e->base.n_ops <= 0) return fail(e, ARCLE_ERR_CONFIG, "no op table installed (arcle_set_op_table)");
+  if (flags & ~0x3ffu) return fail(e, ARCLE_ERR_ARG, "unknown step flag");
+  if (flags & ARCLE_STEP_ROWS_INCREMENTAL) return fail(e, ARCLE_ERR_ARG, "rollouts write every row in full: no ARCLE_STEP_ROWS_INCREMENTAL");
+  const uint32_t outputs = ARCLE_STEP_TRUNCATE | ARCLE_STEP_DENSE | ARCLE_STEP_FLAT_OBS | ARCLE_STEP_PACK_OBS;
+  if ((flags & outputs) && !out) return fail(e, ARCLE_ERR_ARG, "arcle_rollout_ex: output flags without an arcle_rollout_out");
+  if ((flags & (ARCLE_STEP_CONTINUE_RULE | ARCLE_STEP_RESET_ON_SUBMIT)) && ingress != arcle::INGRESS_MASK)
+    return fail(e, ARCLE_ERR_CONFIG, "the rollout kernels take ARCLE_STEP_CONTINUE_RULE / _RESET_ON_SUBMIT with mask ingress only");
+  if ((flags & ARCLE_STEP_CONTINUE_RULE) && !e->bufs.plane[ARCLE_PL_SELECTED])
+    return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_CONTINUE_RULE needs mask ingress and the `selected` plane");
+  if (flags & ARCLE_STEP_TRUNCATE) {
+    if (!out->trunc) return fail(e, ARCLE_ERR_ARG, "ARCLE_STEP_TRUNCATE without arcle_rollout_out.trunc");
+    if (e->base.step_limit <= 0) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_TRUNCATE without a positive step limit (arcle_set_truncation)");
+  }
+  if ((flags & ARCLE_STEP_RESAMPLE) && e->base.n_problems <= 0) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_RESAMPLE without arcle_set_sampler");
+  if (flags & ARCLE_STEP_DENSE) {
+    if (!out->dense) return fail(e, ARCLE_ERR_ARG, "ARCLE_STEP_DENSE without arcle_rollout_out.dense");
+    if (!e->bufs.plane[ARCLE_PL_ANSWER]) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_DENSE needs the answer plane");
+  }
+  const int filtered = (flags & ARCLE_STEP_FLAT_OBS) && out->rows_filtered ? 1 : 0;
+  if (flags & ARCLE_STEP_FLAT_OBS) {
+    const int len = arcle_flat_obs_size(e, filtered);
+    if (len < 0) return fail(e, ARCLE_ERR_CONFIG, "the FilterO2ARC subset needs the O2ARCv2Env state planes");
+    if (!out->rows || (reinterpret_cast<uintptr_t>(out->rows) & 15) || out->rows_stride != ((len + 15) & ~15))
+      return fail(e, ARCLE_ERR_ARG, "arcle_rollout_ex rows: 16-byte aligned int8 [n_steps][n_envs][arcle_flat_obs_size() rounded up to 16]");
+  }
+  if ((flags & ARCLE_STEP_PACK_OBS) && (!out->packed || (reinterpret_cast<uintptr_t>(out->packed) & 15)))
+    return fail(e, ARCLE_ERR_ARG, "arcle_rollout_ex packed: 16-byte aligned uint8 [n_steps][n_envs][arcle_packed_obs_size()]");
+  const size_t n = (size_t)e->cfg.n_envs;
+  if (e->big) {
+    // as arcle_rollout_*: n_steps step launches of the workgroup-per-env kernels, each pointed at its own slices of the outputs
+    // (the handle's installed outputs are restored afterwards)
+    const size_t pb = payload_bytes(e, ingress), rs = (size_t)(out ? out->rows_stride : 0), ps = (size_t)arcle_big::packed_stride(e->base.P);
+    uint8_t* const trunc0 = e->base.trunc;
+    int32_t* const dense0 = e->base.dense;
+    int8_t *const flat0 = e->flat_out, *const pack0 = e->pack_out;
+    const int32_t stride0 = e->flat_stride;
+    const int filt0 = e->flat_filtered, tail0 = e->flat_tail, seq0 = e->flat_seq;
+    int rc = ARCLE_OK;
+    for (int32_t t = 0; t < n_steps && rc == ARCLE_OK; t++) {
+      if (flags & ARCLE_STEP_TRUNCATE) e->base.trunc = out->trunc + (size_t)t * n;
+      if (flags & ARCLE_STEP_DENSE) e->base.dense = out->dense + 2 * (size_t)t * n;
+      if (flags & ARCLE_STEP_FLAT_OBS) {
+        e->flat_out = out->rows + (size_t)t * n * rs;
+        e->flat_stride = out->rows_stride;
+        e->flat_filtered = filtered;
+        e->flat_tail = 0;
+        e->flat_seq = 0;
+      }
+      if (flags & ARCLE_STEP_PACK_OBS) e->pack_out = reinterpret_cast<int8_t*>(out->packed) + (size_t)t * n * ps;
+      rc = launch_step(e, ingress, (const char*)sel + (size_t)t * pb, op + (size_t)t * n, reward + (size_t)t * n, term + (size_t)t * n, flags, stream);
+    }
+    e->base.trunc = trunc0;
+    e->base.dense = dense0;
+    e->flat_out = flat0;
+    e->pack_out = pack0;
+    e->flat_stride = stride0;
+    e->flat_filtered = filt0;
+    e->flat_tail = tail0;
+    e->flat_seq = seq0;
+    return rc;
+  }
+  DeviceGuard guard(e->device);
+  if (e->d_dense_cache) HIP_TRY(e, hipMemsetAsync(e->d_dense_cache, 0, (size_t)e->cfg.n_envs * 8, (hipStream_t)stream));  // (rollouts move grids, keep no pairs)
+  StepParams p = e->base;
+  p.ingress = ingress;
+  p.sel = sel;
+  p.op = op;
+  p.reward = reward;
+  p.term = term;
+  p.flags = flags;
+  p.acct = nullptr;
+  p.rmask = nullptr;
+  p.n_steps = n_steps;
+  p.dense_cache = nullptr;
+  p.trunc = (flags & ARCLE_STEP_TRUNCATE) ? out->trunc : nullptr;
+  p.dense = (flags & ARCLE_STEP_DENSE) ? out->dense : nullptr;
+  p.flat_out = (flags & ARCLE_STEP_FLAT_OBS) ? out->rows : nullptr;
+  p.flat_stride = (flags & ARCLE_STEP_FLAT_OBS) ? out->rows_stride : 0;
+  p.flat_filter = filtered;
+  p.flat_tail = 0;
+  p.flat_seq = 0;
+  p.pack_out = (flags & ARCLE_STEP_PACK_OBS) ? reinterpret_cast<int8_t*>(out->packed) : nullptr;
+  const dim3 g = grid_for(p.n_envs), b(64 * WAVES_PER_WG);
+  hipStream_t st = (hipStream_t)stream;
+  const int fw = width_class(p);
+  int rc;
+  if (ingress == arcle::INGRESS_BBOX) rc = launch_rollout_ing<arcle::INGRESS_BBOX>(fw, g, b, st, p);
+  else if (ingress == arcle::INGRESS_POINT) rc = launch_rollout_ing<arcle::INGRESS_POINT>(fw, g, b, st, p);
+  else rc = launch_rollout_ing<arcle::INGRESS_MASK>(fw, g, b, st, p);
+  if (rc != ARCLE_OK) return fail(e, rc, "this build of libarcle_hip has no rollout kernel for the configuration");
+  HIP_TRY(e, hipGetLastError());
+  return ARCLE_OK;
 }
 
 extern "C" int arcle_set_sampler(arcle_env* e, const int32_t* pair_off, const int32_t* pair_cnt, int32_t n_problems, uint64_t seed,

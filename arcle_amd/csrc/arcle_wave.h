@@ -313,6 +313,10 @@ struct Wave {
   mutable uint32_t stored;  // planes written (through `store`) since the wave picked up its env: what changed in this step
   bool store_nt;            // ARCLE_STEPX_STORE_NT instantiations: plane stores are non-temporal instead of write-through
   bool table;               // expand16 reads the workgroup's LDS table (false: computes the byte masks on the vector ALUs)
+  // rollouts with per-step outputs (wave_rollout, FEAT 1; step_core FEAT 2): the env's episode counter and drawn task live in `ep` / `task`
+  // across the steps instead of memory (load_sampled_task_carried)
+  mutable uint32_t ep;
+  mutable int32_t task;
 
   // (table_: a compile-time constant at every call site — a null test of `lut_` is not: LDS offset 0 is a valid address, and a kernel
   // that cannot fold the test carries both expansions)
@@ -324,6 +328,8 @@ struct Wave {
     issued = 0;
     stored = 0;
     store_nt = false;
+    ep = 0;
+    task = 0;
     ingress = (ingress_ == INGRESS_BBOX5 || ingress_ == INGRESS_BBOX5_PF) ? INGRESS_BBOX : ingress_;  // (the record forms only differ in where the kernel loads from)
     fw = fw_;
     resident = resident_;
@@ -1268,6 +1274,20 @@ ARCLE_DEV bool load_sampled_task(const Wave& w, Rec& r, int env, U4& input_out) 
   }
   return ok;
 }
+// The same inside a rollout (step_core FEAT 2): the counter comes from and goes to w.ep / w.task, which wave_rollout stores once at the end — an env
+// may start several episodes in one launch, and each draw must see the count the previous one left (never re-read from memory).
+ARCLE_DEV bool load_sampled_task_carried(const Wave& w, Rec& r, int env, U4& input_out) {
+  const StepParams& p = w.p;
+  const uint32_t ep = w.ep;
+  const TaskDraw d = draw_task(p.seed, (uint64_t)(p.env_base + env), ep, p.n_problems, p.pair_cnt, p.aug_flags);
+  const int t = p.pair_off[d.problem] + d.sub;
+  const bool ok = load_task(w, r, t, d.rot_k, d.perm, input_out, true);
+  if (ok) {
+    w.ep = ep + 1u;
+    w.task = t;
+  }
+  return ok;
+}
 
 // ------------------------------------------------------------------------------------------------
 // init_state (base.py:155-166 + o2arcenv.py:16-34 / arcenv.py:81-89), counters as in reset (base.py:73-79)
@@ -1366,7 +1386,8 @@ ARCLE_DEV void dense_forget(const Wave& w) {
 // the same code serves the single-step kernel (HBM) and the rollout kernel (register-resident planes).
 // FEAT: 1 = the instantiation also carries the rarely used step flags (ARCLE_STEP_FEATURE_FLAGS: device-side task
 // re-sampling + augmentation, dense reward, continuation rule, reset_on_submit); the plain instantiations (FEAT = 0) keep
-// them out of the hot kernel's code, registers and SGPR spills
+// them out of the hot kernel's code, registers and SGPR spills; 2 = the same inside a rollout with per-step outputs (wave_rollout FEAT 1:
+// task draws count episodes in Wave::ep / task)
 template <int ING, int FW, int ACCT, int FEAT, int FL = -1>
 ARCLE_DEV StepOut step_core(const Wave& w, Rec& r, I2& cnt0, const U4& payload, const int op, const bool early = false,
                             const U4 early_grid = U4{0u, 0u, 0u, 0u}) {
@@ -1390,7 +1411,7 @@ ARCLE_DEV StepOut step_core(const Wave& w, Rec& r, I2& cnt0, const U4& payload, 
       bool ok = true;
       U4 in = u4_zero();
       const bool resample = FEAT && (flags & ARCLE_STEP_RESAMPLE);
-      if (resample) ok = load_sampled_task(w, r, w.env, in);
+      if (resample) ok = FEAT == 2 ? load_sampled_task_carried(w, r, w.env, in) : load_sampled_task(w, r, w.env, in);
       if (ok) init_state(w, r, cnt0, resample, in);
       else raise_status(p, out, ARCLE_ST_AUG_DOMAIN);
       if (FEAT && (flags & ARCLE_STEP_DENSE)) {
@@ -1960,9 +1981,24 @@ ARCLE_DEV void wave_step(Wave& w, int env, StepInputs& in, uint64_t t_entry = 0,
 // out, plus the action in and 5 B of reward/terminated out per step.
 //   sel: int32 [n_steps][n_envs][4|2] | int8 [n_steps][n_envs][P]   op: int32 [n_steps][n_envs]
 //   reward: int32 [n_steps][n_envs]     term: uint8 [n_steps][n_envs]
+// FEAT 1 (arcle_rollout_ex): the body also runs the research env's step flags (ARCLE_ROLLOUT_FEAT_FLAGS: TimeLimit, device-side
+// resampling, dense pair, flat rows) with their outputs per step, slice t of
+//   trunc: uint8 [n_steps][n_envs]   dense: int32 [n_steps][n_envs][2]   flat_out: int8 [n_steps][n_envs][flat_stride] (full rows, no tail)
+// An env may start several episodes in one launch: its episode counter and drawn task stay in registers (Wave::ep / task) and are
+// stored once at the end.  FEAT -1 (the CPU emulator's form) picks the body from the launch's flags, as the launcher picks the kernel.
 // ------------------------------------------------------------------------------------------------
-template <int ING, int FW, int FL = -1>
-ARCLE_DEV void wave_rollout(const StepParams& p, WaveLDS* lds, const U2* lut, int env, int lane) {
+#define ARCLE_ROLLOUT_FEAT_FLAGS (ARCLE_STEP_TRUNCATE | ARCLE_STEP_RESAMPLE | ARCLE_STEP_DENSE | ARCLE_STEP_FLAT_OBS)
+template <int ING, int FW, int FL = -1, int FEAT = -1>
+ARCLE_DEV void wave_rollout(const StepParams& p0, WaveLDS* lds, const U2* lut, int env, int lane) {
+  if constexpr (FEAT < 0) {
+    if (((FL >= 0 ? (uint32_t)FL : p0.flags) & ARCLE_ROLLOUT_FEAT_FLAGS) != 0u) wave_rollout<ING, FW, FL, 1>(p0, lds, lut, env, lane);
+    else wave_rollout<ING, FW, FL, 0>(p0, lds, lut, env, lane);
+  } else {
+  // FEAT 1: the step body writes the dense pair and the flat row at [env] of p.dense / p.flat_out — a copy of the parameters whose two
+  // bases move to slice t before step t (the plain body reads the launch's parameters as they are)
+  StepParams q;
+  if constexpr (FEAT) q = p0;
+  const StepParams& p = FEAT ? q : p0;
   Wave w(p, lds, lut, lane, ING, FW, false);
   w.set_env(env);
 #pragma unroll
@@ -1971,6 +2007,12 @@ ARCLE_DEV void wave_rollout(const StepParams& p, WaveLDS* lds, const U2* lut, in
   Rec r = load_rec(p, env);
   I2 cnt = load_cnt(p, env);
   const size_t N = (size_t)p.n_envs;
+  const uint32_t flags = FL >= 0 ? ((uint32_t)FL & 0xffffu) : p.flags;
+  uint32_t ep0 = 0;
+  if (FEAT && (flags & ARCLE_STEP_RESAMPLE)) {  // (read once, before anything of this launch wrote it)
+    ep0 = xl::uniform((uint32_t)p.episode[env]);
+    w.ep = ep0;
+  }
   // The next action is fetched while the current one executes (through VGPRs: vector loads of a uniform address +
   // readfirstlane at use, so that the in-order vmcnt lets the op body run under the load).
   U4 next_payload = load_payload_v(w, env, 0);
@@ -1986,13 +2028,20 @@ ARCLE_DEV void wave_rollout(const StepParams& p, WaveLDS* lds, const U2* lut, in
       next_payload = load_payload_v(w, env, (size_t)t + 1);
       next_op = (uint32_t)p.op[((size_t)t + 1) * N + env];
     }
-    // (the feature flags a rollout accepts — continuation rule, reset_on_submit — belong to mask-ingress trace replay;
+    if constexpr (FEAT) {
+      if (flags & ARCLE_STEP_DENSE) q.dense = p0.dense + 2 * ((size_t)t * N);
+      if (flags & ARCLE_STEP_FLAT_OBS) q.flat_out = p0.flat_out + (size_t)t * N * (size_t)p0.flat_stride;
+    }
+    // (the feature flags a plain rollout accepts — continuation rule, reset_on_submit — belong to mask-ingress trace replay;
     //  FL >= 0: the flag set is a compile-time constant of this instantiation, as in the step kernel)
-    const StepOut out = step_core<ING, FW, 0, is_cells(ING) ? 1 : 0, FL>(w, r, cnt, payload, op);
+    const StepOut out = step_core<ING, FW, 0, FEAT ? 2 : (is_cells(ING) ? 1 : 0), FL>(w, r, cnt, payload, op);
     if (lane == 0) {
       p.reward[(size_t)t * N + env] = out.reward;
       p.term[(size_t)t * N + env] = (uint8_t)out.term;
+      if (FEAT && (flags & ARCLE_STEP_TRUNCATE)) p.trunc[(size_t)t * N + env] = (uint8_t)(cnt.x >= p.step_limit);
     }
+    // the fused observation row of this step out of the registers the state lives in (always in full: no incremental rows)
+    if (FEAT && (flags & ARCLE_STEP_FLAT_OBS)) flat_row(w, r);
     // ARCLE_STEP_PACK_OBS (round 5): the packed observation row of EVERY step — grid | grid_dim | reward | terminated, what a learner gathers —
     // out of the registers the state lives in: pack_out is [n_steps][n_envs][packed stride]; the Gym contract "an observation after every
     // step" without leaving the chip between the steps
@@ -2007,6 +2056,11 @@ ARCLE_DEV void wave_rollout(const StepParams& p, WaveLDS* lds, const U2* lut, in
   xl::lanes_converged();
   store_rec(p, env, lane, r);
   store_cnt(p, env, lane, cnt);
+  if (FEAT && (flags & ARCLE_STEP_RESAMPLE) && w.ep != ep0 && lane == 0) {  // the episodes this launch started: counter and task, stored once
+    p.episode[env] = (int32_t)w.ep;
+    if (p.cur_task) p.cur_task[env] = w.task;
+  }
+  }
 }
 
 // ------------------------------------------------------------------------------------------------

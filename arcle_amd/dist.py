@@ -28,7 +28,7 @@ env.step_bbox(..., group=g)`): two free-running groups on two queues overlap one
 import torch
 import torch.distributed as dist
 
-from .engine import EnvBatch
+from .engine import EnvBatch, capture_guard
 
 
 def shard_range(global_envs, world_size, rank):
@@ -254,7 +254,7 @@ class ShardedVecEnv:
         side = torch.cuda.Stream(self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
+        with capture_guard(), torch.cuda.graph(g, stream=side):
             for i in range(K):
                 b.set_packed_output(packed[i][:grp.n])
                 env._enqueue_steps(form, payload[i:i + 1], None if operation is None else operation[i:i + 1], reward[i:i + 1],

@@ -4,7 +4,9 @@
 layout include/arcle_hip.h declares and hands their raw pointers to the C ABI.  All stepping happens
 in the HIP kernels; this file contains no grid arithmetic.
 """
+import contextlib
 import ctypes
+import gc
 import os
 
 import numpy as np
@@ -61,6 +63,22 @@ def check_grid_size(H, W):
 
 
 _hip = None
+
+
+@contextlib.contextmanager
+def capture_guard():
+    """Wrap every hipGraph capture of the package.  Python finalizers must not run while a capture is under way: an EnvBatch that
+    dies at a garbage collection (an ARCVecEnv with a task sampler holds reference cycles, so it dies then and not at its last
+    reference) frees its device buffers with hipFree, a synchronising call, and that invalidates the capture.  Dead objects are
+    therefore collected first and the collector stays off until the capture has ended."""
+    was_enabled = gc.isenabled()
+    gc.collect()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 def _ptr(t):
@@ -427,6 +445,56 @@ class EnvBatch:
         fn = self.L.arcle_rollout_mask if mask else (self.L.arcle_rollout_point if point else self.L.arcle_rollout_bbox)
         self._check(fn(self._h, T, _ptr(payload), _ptr(op), _ptr(reward), _ptr(term), int(flags), self._stream()),
                     "arcle_rollout")
+        return reward, term
+
+    def rollout_ex(self, payload, op, flags, form, trunc=None, dense=None, rows=None, rows_filtered=False, packed=None):
+        """T steps in one launch with the research env's step flags (arcle_rollout_ex): same semantics as T step_* calls with `flags`,
+        every step's outputs written to caller-allocated device tensors — trunc uint8 [T,N] (STEP_TRUNCATE), dense int32 [T,N,2]
+        (STEP_DENSE), rows int8 [T,N,stride] (STEP_FLAT_OBS; stride = flat_obs_size(rows_filtered) rounded up to 16, rows written in full),
+        packed uint8 [T,N,packed_obs_size()] (STEP_PACK_OBS).  form "bbox" (int32 [T,N,4]) | "point" (int32 [T,N,2]) | "mask" (int8
+        [T,N,H,W]); op int32 [T,N].  Every tensor is checked before anything is launched (ValueError); an output flag whose tensor is missing
+        is refused by the library.  Returns (reward int32 [T,N], terminated uint8 [T,N])."""
+        if form not in ("bbox", "point", "mask"):
+            raise ValueError(f"rollout_ex: form must be 'bbox', 'point' or 'mask', got {form!r}")
+        if not torch.is_tensor(op) or op.dim() != 2:
+            raise ValueError("rollout_ex: op must be an int32 [T, N] device tensor")
+        T = int(op.shape[0])
+        if T <= 0:
+            raise ValueError("rollout_ex: at least one step")
+        N = self.N
+
+        def check(name, t, shape, dtype):
+            if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+                got = (tuple(t.shape), t.dtype, str(t.device), t.is_contiguous()) if torch.is_tensor(t) else type(t).__name__
+                raise ValueError(f"rollout_ex: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {self.device}, got {got}")
+
+        pay_shape = {"bbox": (T, N, 4), "point": (T, N, 2), "mask": (T, N, self.H, self.W)}[form]
+        check("payload", payload, pay_shape, torch.int8 if form == "mask" else torch.int32)
+        check("op", op, (T, N), torch.int32)
+        flags = int(flags)
+        outs = {"trunc": (trunc, STEP_TRUNCATE), "dense": (dense, STEP_DENSE), "rows": (rows, STEP_FLAT_OBS), "packed": (packed, STEP_PACK_OBS)}
+        for name, (t, bit) in outs.items():
+            if t is not None and not flags & bit:
+                raise ValueError(f"rollout_ex: {name} given without its step flag")
+        if trunc is not None:
+            check("trunc", trunc, (T, N), torch.uint8)
+        if dense is not None:
+            check("dense", dense, (T, N, 2), torch.int32)
+        stride = 0
+        if rows is not None:
+            stride = (self.flat_obs_size(rows_filtered) + 15) & ~15
+            check("rows", rows, (T, N, stride), torch.int8)
+            if rows.data_ptr() % 16:
+                raise ValueError("rollout_ex: rows must be 16-byte aligned")
+        if packed is not None:
+            check("packed", packed, (T, N, self.packed_obs_size()), torch.uint8)
+            if packed.data_ptr() % 16:
+                raise ValueError("rollout_ex: packed must be 16-byte aligned")
+        reward = torch.empty((T, N), dtype=torch.int32, device=self.device)
+        term = torch.empty((T, N), dtype=torch.uint8, device=self.device)
+        out = _lib.RolloutOut(_ptr(trunc), _ptr(dense), _ptr(rows), stride, int(bool(rows_filtered)), _ptr(packed))
+        self._check(self.L.arcle_rollout_ex(self._h, _lib.INGRESS[form], T, _ptr(payload), _ptr(op), _ptr(reward), _ptr(term),
+                                            ctypes.byref(out), flags, self._stream()), "arcle_rollout_ex")
         return reward, term
 
     def flat_obs_size(self, filtered=False):

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from .. import actions, sampling
-from ..engine import (AUG_PERMUTE, AUG_ROT90, EnvBatch, STEP_AUTORESET, STEP_DENSE, STEP_FLAT_OBS, STEP_PACK_OBS, STEP_RESAMPLE,
+from ..engine import (AUG_PERMUTE, AUG_ROT90, EnvBatch, capture_guard, STEP_AUTORESET, STEP_DENSE, STEP_FLAT_OBS, STEP_PACK_OBS, STEP_RESAMPLE,
                       STEP_RESET_ON_SUBMIT, STEP_ROWS_INCREMENTAL, STEP_TRUNCATE, ST_AUG_DOMAIN, ST_BAD_OP, ST_BAD_SELECTION, ST_BAD_TASK, ST_ROTATE_DOMAIN,
                       check_grid_size)
 
@@ -523,7 +523,7 @@ class ARCVecEnv:
         side = torch.cuda.Stream(self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
+        with capture_guard(), torch.cuda.graph(g, stream=side):
             self._enqueue_steps(form, payload, operation, reward, term, trunc, dense)
             r = self._dense(reward, dense) if dense is not None else reward
         tr = trunc.view(torch.bool) if trunc is not None else torch.zeros_like(term, dtype=torch.bool)
@@ -604,6 +604,50 @@ class ARCVecEnv:
             raise NotImplementedError("rollouts support plain and same-task autoreset envs with device-only op tables")
         # (only the final state of a rollout is observable: no per-step packed / flat rows — the callers refresh the live rows afterwards)
         return self.flags & ~(STEP_PACK_OBS | STEP_FLAT_OBS | STEP_ROWS_INCREMENTAL)
+
+    def rollout(self, payload, operation=None, form="bbox", rows=None, rows_kind="filtered"):
+        """T steps of this env — in ANY configuration, the research env's included (autoreset="resample", max_episode_steps,
+        dense_reward, augment) — in ONE launch: step_many's contract.  payload [T, N, ...] in the action form `form` ("bbox" int32
+        [T,N,4] | "point" [T,N,2] | "mask" int8 [T,N,H,W] | "bbox5" int32 [T,N,5], split into bbox and operation on the device),
+        operation int32 [T, N] (None for "bbox5").  Returns (obs, reward [T,N], terminated [T,N], truncated [T,N], info): obs / info
+        (and the enable_flat_rows mirror) describe the state after the LAST step; reward is float32 from the dense pairs when
+        dense_reward=True.  rows: an optional device tensor that receives EVERY step's observation row — rows_kind "filtered" / "full":
+        int8 [T, N, stride] FlattenObservation rows (stride = batch.flat_obs_size(filtered) rounded up to 16); "packed": uint8
+        [T, N, batch.packed_obs_size()] rows grid | grid_dim | reward | terminated."""
+        if self._host_slots:
+            raise NotImplementedError("rollouts need a device-only op table (no host callables)")
+        if rows_kind not in ("filtered", "full", "packed"):
+            raise ValueError("rows_kind: 'filtered', 'full' or 'packed'")
+        if form == "bbox5":
+            if not torch.is_tensor(payload) or payload.dim() != 3 or payload.shape[1:] != (self.N, 5) or payload.dtype != torch.int32 \
+                    or payload.device != self.device:
+                raise ValueError(f"rollout: bbox5 records must be an int32 [T, {self.N}, 5] tensor on {self.device}")
+            payload, operation, form = payload[..., :4].contiguous(), payload[..., 4].contiguous(), "bbox"
+        elif form not in ("bbox", "point", "mask"):
+            raise ValueError(f"rollout: unknown action form {form!r}")
+        b = self.batch
+        flags = self.flags & ~(STEP_PACK_OBS | STEP_FLAT_OBS | STEP_ROWS_INCREMENTAL)
+        kw = {}
+        if rows is not None:
+            if rows_kind == "packed":
+                flags |= STEP_PACK_OBS
+                kw["packed"] = rows
+            else:
+                flags |= STEP_FLAT_OBS
+                kw["rows"], kw["rows_filtered"] = rows, rows_kind == "filtered"
+        T = int(operation.shape[0]) if torch.is_tensor(operation) else 0
+        trunc = dense = None
+        if self.max_episode_steps is not None:
+            trunc = torch.zeros((T, self.N), dtype=torch.uint8, device=self.device)
+        if self.dense_reward:
+            dense = torch.zeros((T, self.N, 2), dtype=torch.int32, device=self.device)
+        reward, term = b.rollout_ex(payload, operation, flags, form, trunc=trunc, dense=dense, **kw)
+        self._refresh_rows()  # (the live mirror is rewritten from the final state)
+        if self.flags & STEP_PACK_OBS:  # ... and so is the installed packed row (the last step's reward / terminated)
+            b._check(b.L.arcle_pack_obs(b._h, reward[-1].data_ptr(), term[-1].data_ptr(), b.packed.data_ptr(), b._stream()), "arcle_pack_obs")
+        r = self._dense(reward, dense) if dense is not None else reward
+        tr = trunc.view(torch.bool) if trunc is not None else torch.zeros_like(term, dtype=torch.bool)
+        return self._obs, r, term.view(torch.bool), tr, self._info()
 
     def flat_obs(self, out=None, filtered=False):
         """The observation as one [N, L] int8 tensor in FlattenObservation key order (what the reference's policies

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ARCLE_ABI_VERSION 5
+#define ARCLE_ABI_VERSION 6
 #define ARCLE_MAX_OPS 64
 #define ARCLE_MAX_CELLS 1024 /* H*W <= 1024: one 64-lane wavefront x 16 cells holds a plane (the one-wavefront-per-env kernels);
                                 larger planes (H, W <= 127) are served by the workgroup-per-env kernels — see "Grids beyond
@@ -344,6 +344,30 @@ int arcle_rollout_point(arcle_env* env, int32_t n_steps, const int32_t* xy, cons
  * tests/o2arc_check.py:139-199 of the reference) */
 int arcle_rollout_mask(arcle_env* env, int32_t n_steps, const int8_t* sel, const int32_t* op, int32_t* reward,
                        uint8_t* term, uint32_t flags, void* stream);
+
+/* (ABI 6) The same rollout with the research env's step flags and EVERY step's outputs: identical to n_steps calls of arcle_step_*
+ * with the same flags, the rows written in full.  ingress ARCLE_INGRESS_BBOX | _POINT | _MASK (sel as above).
+ * flags: everything a step accepts except ARCLE_STEP_ROWS_INCREMENTAL (the mask-only rules of CONTINUE_RULE / RESET_ON_SUBMIT hold);
+ * TRUNCATE takes the step limit installed with arcle_set_truncation (positive), RESAMPLE the sampler of arcle_set_sampler.  Step t writes
+ * slice t of every output of `out`, device arrays the caller owns (the arrays installed with the setters are not written):
+ *   trunc   uint8 [n_steps][n_envs]                                           (ARCLE_STEP_TRUNCATE)
+ *   dense   int32 [n_steps][n_envs][2]                                        (ARCLE_STEP_DENSE)
+ *   rows    int8  [n_steps][n_envs][rows_stride], rows_stride = arcle_flat_obs_size(env, rows_filtered) rounded up to 16, 16-byte
+ *           aligned, no tail                                                  (ARCLE_STEP_FLAT_OBS)
+ *   packed  uint8 [n_steps][n_envs][arcle_packed_obs_size()], 16-byte aligned (ARCLE_STEP_PACK_OBS)
+ * An env may end several episodes inside one launch; episode / cur_task of the sampler describe the state after the last step.  The
+ * dense-pair cache is dropped (as by every rollout).  A missing output, a wrong stride, TRUNCATE without a positive step limit, RESAMPLE
+ * without a sampler or ROWS_INCREMENTAL is refused (ARCLE_ERR_ARG / _CONFIG) before anything is enqueued. */
+typedef struct {
+  uint8_t* trunc;
+  int32_t* dense;
+  int8_t* rows;
+  int32_t rows_stride;
+  int32_t rows_filtered;
+  uint8_t* packed;
+} arcle_rollout_out;
+int arcle_rollout_ex(arcle_env* env, int ingress, int32_t n_steps, const void* sel, const int32_t* op, int32_t* reward, uint8_t* term,
+                     const arcle_rollout_out* out, uint32_t flags, void* stream);
 
 /* Device-side task choice.  pair_off / pair_cnt: device int32 [n_problems] — first task-table entry and number of
  * entries (pairs) of every problem that has at least one (Loader.pick's candidates for the current adaptation mode);
