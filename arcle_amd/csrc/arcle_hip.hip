@@ -4,6 +4,7 @@
 //   arcle_step_kernel          one step() of every env; 4 or 8 waves per workgroup (plan_launch); the launches of the standard batch order
 //                              themselves inside groups of 32 envs (the GROUPED block)
 //   arcle_transition_rows_kernel  the stateless transition(state, action) on flattened state rows
+//   arcle_expand_kernel        K candidate actions per state row, verdicts and child hashes only (arcle_search.h); arcle_hash_rows_kernel
 //   arcle_rollout_kernel       n_steps step()s per launch with the env state resident in registers
 //   arcle_reset[_table]_kernel init_state for (masked) envs, optionally from the device task table / device-drawn tasks
 //   arcle_flatten_kernel       flattened observation rows (also an epilogue of the step kernel: ARCLE_STEP_FLAT_OBS)
@@ -203,6 +204,7 @@ __device__ __forceinline__ void sink_v(uint32_t v) { asm volatile("" ::"v"(v)); 
 }  // namespace xl
 
 #include "arcle_wave.h"
+#include "arcle_search.h"      // state hash + K-actions-per-row expansion (arcle_hash_rows / arcle_expand_rows)
 #include "arcle_big_params.h"  // grids beyond ARCLE_MAX_CELLS: one workgroup per env (arcle_big.hip)
 
 using arcle::StepParams;
@@ -527,6 +529,33 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) void arcle_transition_rows_kerne
   arcle::wave_transition_row<ING, FW>(p, &lds.wave[threadIdx.x >> 6], lds.lut, row, (int)(threadIdx.x & 63));
 }
 
+__global__ __launch_bounds__(64 * WAVES_PER_WG) void arcle_hash_rows_kernel(const arcle::ExpandParams x) {
+  __shared__ BlockLDS lds;
+  const int row = wave_of_launch();
+  if (row >= x.p.n_envs) return;
+  arcle::wave_hash_row(x, &lds.wave[threadIdx.x >> 6], lds.lut, row, (int)(threadIdx.x & 63));
+}
+
+// wave v of the launch expands actions [j * chunk, (j + 1) * chunk) of parent row m, v = m * n_chunks + j: the waves of one parent are
+// neighbours (its row is read from HBM once and from the L2 after that)
+// (2 waves per SIMD = up to 256 VGPRs: the loop over the actions carries the parent's planes, their hash terms and whatever the
+// compiler hoists out of the step body — 256 VGPRs, no scratch in the bbox / fast-width instantiation.  Held to 3, 4 or 8 waves per SIMD the kernel spills
+// 228 / 380 / 672 B per lane to scratch and is slower at every size: profiles/expand_bench.txt)
+#ifndef ARCLE_EXPAND_WAVES_PER_EU
+#define ARCLE_EXPAND_WAVES_PER_EU 2
+#endif
+template <int ING, int FW>
+__global__ __launch_bounds__(64 * WAVES_PER_WG) __attribute__((amdgpu_waves_per_eu(ARCLE_EXPAND_WAVES_PER_EU))) void arcle_expand_kernel(const arcle::ExpandParams x) {
+  __shared__ BlockLDS lds;
+  arcle::lut_init(lds.lut, (int)threadIdx.x);
+  xl::wg_barrier();
+  const uint32_t v = (uint32_t)wave_of_launch();
+  if (v >= (uint32_t)x.p.n_envs * (uint32_t)x.n_chunks) return;
+  const uint32_t m = v / (uint32_t)x.n_chunks, j = v - m * (uint32_t)x.n_chunks;
+  const int k0 = (int)j * x.chunk, k1 = k0 + x.chunk < x.n_actions ? k0 + x.chunk : x.n_actions;
+  arcle::wave_expand_row<ING, FW>(x, &lds.wave[threadIdx.x >> 6], lds.lut, (int)m, k0, k1, (int)(threadIdx.x & 63));
+}
+
 __global__ __launch_bounds__(64 * WAVES_PER_WG) void arcle_reset_kernel(const StepParams p) {
   __shared__ BlockLDS lds;
   const int env = wave_of_launch();
@@ -734,7 +763,8 @@ extern "C" int arcle_create(const arcle_config* cfg, const arcle_buffers* bufs, 
       return ARCLE_ERR_HIP;
     }
   }
-  if (hipMalloc((void**)&e->d_status, 8) != hipSuccess || hipMemset(e->d_status, 0, 8) != hipSuccess ||
+  // (d_status[0] the sticky word, [1] arcle_get_status' read-back, [2] the scratch word speculative launches raise their bits into)
+  if (hipMalloc((void**)&e->d_status, 16) != hipSuccess || hipMemset(e->d_status, 0, 16) != hipSuccess ||
       hipMalloc((void**)&e->d_ops, sizeof(uint32_t) * (ARCLE_MAX_OPS + 1)) != hipSuccess ||  // (+1: slot n_ops is always an empty one)
       hipMemset(e->d_ops, 0, sizeof(uint32_t) * (ARCLE_MAX_OPS + 1)) != hipSuccess) {
     arcle_destroy(e);
@@ -2068,6 +2098,107 @@ extern "C" int arcle_transition_rows(arcle_env* e, int32_t n_rows, const int8_t*
     case arcle::INGRESS_MASK: launch_transition_ing<arcle::INGRESS_MASK>(fw, g, b, st, p); break;
     default: return fail(e, ARCLE_ERR_ARG, "arcle_transition_rows takes mask, bbox or point selections");
   }
+  HIP_TRY(e, hipGetLastError());
+  return ARCLE_OK;
+}
+
+// ---- search on state rows: hashes, and K candidate actions per row without materialising the children (arcle_search.h) ------
+extern "C" int arcle_hash_rows(arcle_env* e, int32_t n_rows, const int8_t* rows, int32_t stride, uint64_t* hash, void* stream) {
+  if (!e || !hash) return ARCLE_ERR_ARG;
+  if (n_rows <= 0) return fail(e, ARCLE_ERR_ARG, "n_rows must be positive");
+  if (e->big) return fail(e, ARCLE_ERR_CONFIG, "arcle_hash_rows: handles of at most 1024 cells per plane (ARCLE_MAX_CELLS)");
+  if (int rc = check_rows(e, rows, stride, 0)) return rc;
+  DeviceGuard guard(e->device);
+  arcle::ExpandParams x = {};
+  x.p = e->base;
+  x.p.n_envs = n_rows;
+  x.p.rows_in = rows;
+  x.p.rows_in_stride = stride;
+  x.hash = hash;
+  hipLaunchKernelGGL(arcle_hash_rows_kernel, grid_for(n_rows), dim3(64 * WAVES_PER_WG), 0, (hipStream_t)stream, x);
+  HIP_TRY(e, hipGetLastError());
+  return ARCLE_OK;
+}
+
+template <int ING>
+static void launch_expand_ing(int fw, dim3 g, dim3 b, hipStream_t st, const arcle::ExpandParams& x) {
+  // (planes live in registers: FW_FULL shares FW_FAST's code, as in the row and rollout kernels)
+  if (fw != arcle::FW_GENERIC) hipLaunchKernelGGL((arcle_expand_kernel<ING, arcle::FW_FAST>), g, b, 0, st, x);
+  else hipLaunchKernelGGL((arcle_expand_kernel<ING, arcle::FW_GENERIC>), g, b, 0, st, x);
+}
+
+// Actions per wavefront.  A wave pays one pass over its parent's planes (7 loads + their hash terms) before its first action, so
+// large K wants long chunks; a small frontier wants M * ceil(K / chunk) waves to cover the chip.  The rule aims at ARCLE_EXPAND_WAVES
+// waves per launch — ONE occupancy round: 1024 SIMDs x the 2 waves per SIMD the kernel compiles to — and never splits below one
+// action: chunk = M * K / 2048 clamped to [1, K], then evened out over the chunks.  Measured (profiles/expand_bench.txt): half a
+// round (chunk x 2) and two rounds (chunk / 2) both lose 20-60 % at (M, K) = (1024, 32), (256, 256) and (64, 1024).
+#ifndef ARCLE_EXPAND_WAVES
+#define ARCLE_EXPAND_WAVES 2048
+#endif
+static int expand_chunk(int64_t M, int64_t K) {
+  int64_t c = M * K / ARCLE_EXPAND_WAVES;
+  if (const char* s = getenv("ARCLE_EXPAND_CHUNK"))  // (tuning runs)
+    if (atoi(s) > 0) c = atoi(s);
+  c = c < 1 ? 1 : c > K ? K : c;
+  const int64_t n = (K + c - 1) / c;
+  return (int)((K + n - 1) / n);
+}
+
+extern "C" int arcle_expand_rows(arcle_env* e, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t n_actions, int ingress,
+                                 const void* sel, const int32_t* op, int32_t action_row_stride, const int32_t* src_env, int32_t* reward,
+                                 uint8_t* term, uint8_t* status, uint64_t* hash, int32_t* dense, uint64_t* parent_hash, uint32_t flags,
+                                 void* stream) {
+  if (!e || !sel || !op || !reward || !term || !status || !hash) return ARCLE_ERR_ARG;
+  if (n_rows <= 0 || n_actions <= 0) return fail(e, ARCLE_ERR_ARG, "n_rows and n_actions must be positive");
+  if (action_row_stride != 0 && action_row_stride != n_actions)
+    return fail(e, ARCLE_ERR_ARG, "action_row_stride: 0 (one action set for every row) or n_actions (a set per row)");
+  if (ingress != arcle::INGRESS_BBOX && ingress != arcle::INGRESS_POINT) return fail(e, ARCLE_ERR_ARG, "arcle_expand_rows takes bbox or point selections");
+  if (e->big) return fail(e, ARCLE_ERR_CONFIG, "arcle_expand_rows: handles of at most 1024 cells per plane (ARCLE_MAX_CELLS); larger grids expand through arcle_transition_rows");
+  if (!src_env && n_rows > e->cfg.n_envs) return fail(e, ARCLE_ERR_ARG, "more rows than envs: pass src_env (which env's answer every row uses)");
+  if ((int64_t)n_rows * n_actions >= (1ll << 28)) return fail(e, ARCLE_ERR_ARG, "too many children (n_rows * n_actions < 2^28)");
+  if (e->base.n_ops <= 0) return fail(e, ARCLE_ERR_CONFIG, "no op table installed (arcle_set_op_table)");
+  if (dense) flags |= ARCLE_STEP_DENSE;
+  if (flags & ~(ARCLE_STEP_RESET_ON_SUBMIT | ARCLE_STEP_DENSE | ARCLE_STEP_CONTINUE_RULE))
+    return fail(e, ARCLE_ERR_ARG, "arcle_expand_rows takes ARCLE_STEP_RESET_ON_SUBMIT / _DENSE only");
+  if (flags & ARCLE_STEP_CONTINUE_RULE) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_CONTINUE_RULE needs mask ingress");
+  if ((flags & ARCLE_STEP_DENSE) && !dense) return fail(e, ARCLE_ERR_ARG, "ARCLE_STEP_DENSE without a dense output array");
+  if ((flags & ARCLE_STEP_DENSE) && !e->bufs.plane[ARCLE_PL_ANSWER]) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_DENSE needs the answer plane");
+  if (int rc = check_rows(e, rows, stride, 0)) return rc;
+  DeviceGuard guard(e->device);
+  arcle::ExpandParams x = {};
+  StepParams& p = x.p;
+  p = e->base;
+  p.n_resident = p.n_envs;
+  p.n_envs = n_rows;
+  p.ingress = ingress;
+  p.sel = sel;
+  p.op = op;
+  p.reward = reward;
+  p.term = term;
+  p.flags = flags;
+  p.acct = nullptr;
+  p.rmask = nullptr;
+  p.task_idx = src_env;
+  p.rows_in = rows;
+  p.rows_in_stride = stride;
+  p.dense = dense;
+  p.dense_cache = nullptr;
+  p.flat_out = nullptr;
+  p.pack_out = nullptr;
+  p.trunc = nullptr;
+  p.status = e->d_status + 2;  // expansion is speculation: the handle's sticky word stays as it is
+  x.n_actions = n_actions;
+  x.action_row_stride = action_row_stride;
+  x.chunk = expand_chunk(n_rows, n_actions);
+  x.n_chunks = (n_actions + x.chunk - 1) / x.chunk;
+  x.status_out = status;
+  x.hash = hash;
+  x.parent_hash = parent_hash;
+  const dim3 g = grid_for(n_rows * x.n_chunks), b(64 * WAVES_PER_WG);
+  hipStream_t st = (hipStream_t)stream;
+  const int fw = width_class(e->base);
+  if (ingress == arcle::INGRESS_BBOX) launch_expand_ing<arcle::INGRESS_BBOX>(fw, g, b, st, x);
+  else launch_expand_ing<arcle::INGRESS_POINT>(fw, g, b, st, x);
   HIP_TRY(e, hipGetLastError());
   return ARCLE_OK;
 }

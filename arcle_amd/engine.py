@@ -4,6 +4,7 @@
 layout include/arcle_hip.h declares and hands their raw pointers to the C ABI.  All stepping happens
 in the HIP kernels; this file contains no grid arithmetic.
 """
+import collections
 import contextlib
 import ctypes
 import gc
@@ -83,6 +84,10 @@ def capture_guard():
 
 def _ptr(t):
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
+
+
+# what EnvBatch.expand_rows returns: device tensors [M, K, ...] (dense None without the dense pair; parent_hash [M, 2])
+Expansion = collections.namedtuple("Expansion", "reward term status hash dense parent_hash")
 
 
 class EnvBatch:
@@ -578,6 +583,51 @@ class EnvBatch:
                                                  _ptr(src_env), _ptr(out), stride, int(tail), _ptr(reward), _ptr(term), int(flags),
                                                  self._stream()), "arcle_transition_rows")
         return out, reward, term
+
+    # ---- search on state rows: hashes, K candidate actions per row ---------------------------------------------------------------
+    def hash_rows(self, rows, out=None):
+        """(state_hash, grid_hash) of every state row: rows int8 [M, >= L] (any stride / alignment) -> int64 [M, 2] (the uint64
+        words of arcle_hash_rows reinterpreted: torch sorts, compares and `unique`s int64).  The formula: include/arcle_hip.h;
+        its NumPy mirror: arcle_amd.search.hash_rows_numpy."""
+        M = int(rows.shape[0])
+        assert rows.dtype == torch.int8 and rows.dim() == 2 and rows.stride(1) == 1
+        if out is None:
+            out = torch.empty((M, 2), dtype=torch.int64, device=self.device)
+        assert out.dtype == torch.int64 and tuple(out.shape) == (M, 2) and out.is_contiguous()
+        self._check(self.L.arcle_hash_rows(self._h, M, _ptr(rows), rows.stride(0), _ptr(out), self._stream()), "arcle_hash_rows")
+        return out
+
+    def expand_rows(self, rows, form, payload, op, src_env=None, dense=False, flags=0, out=None):
+        """K candidate actions per state row, verdicts only (arcle_expand_rows): rows int8 [M, >= L], read only; form "bbox" | "point";
+        payload int32 [K, 4 | 2] with op int32 [K] (ONE action set applied to every row) or [M, K, 4 | 2] with op [M, K] (a set per
+        row); src_env int32 [M] = the env whose answer row m is judged against (None: env m).  Returns an Expansion of device tensors,
+        all [M, K, ...]: reward int32, term uint8, status uint8 (ARCLE_ST_* bits of that child), hash int64 [M, K, 2] (state_hash,
+        grid_hash of the child row, which is never written), dense int32 [M, K, 2] (correct, total) or None, parent_hash int64 [M, 2].
+        Every value equals what transition_rows + hash_rows report for the replicated (row, action) pairs.  out: an Expansion of a
+        previous call with the same shapes to write into (captured graphs)."""
+        assert form in ("bbox", "point"), "expand_rows takes bbox or point actions"
+        M = int(rows.shape[0])
+        tw = 4 if form == "bbox" else 2
+        assert rows.dtype == torch.int8 and rows.dim() == 2 and rows.stride(1) == 1
+        assert payload.dtype == torch.int32 and payload.is_contiguous() and op.dtype == torch.int32 and op.is_contiguous()
+        if payload.dim() == 2:
+            K, stride = int(payload.shape[0]), 0
+            assert tuple(payload.shape) == (K, tw) and tuple(op.shape) == (K,)
+        else:
+            K = int(payload.shape[1])
+            stride = K
+            assert tuple(payload.shape) == (M, K, tw) and tuple(op.shape) == (M, K)
+        if out is None:
+            dev = self.device
+            out = Expansion(torch.empty((M, K), dtype=torch.int32, device=dev), torch.empty((M, K), dtype=torch.uint8, device=dev),
+                            torch.empty((M, K), dtype=torch.uint8, device=dev), torch.empty((M, K, 2), dtype=torch.int64, device=dev),
+                            torch.empty((M, K, 2), dtype=torch.int32, device=dev) if dense else None,
+                            torch.empty((M, 2), dtype=torch.int64, device=dev))
+        assert tuple(out.reward.shape) == (M, K) and (out.dense is not None) == bool(dense)
+        self._check(self.L.arcle_expand_rows(self._h, M, _ptr(rows), rows.stride(0), K, _lib.INGRESS[form], _ptr(payload), _ptr(op), stride,
+                                             _ptr(src_env), _ptr(out.reward), _ptr(out.term), _ptr(out.status), _ptr(out.hash),
+                                             _ptr(out.dense), _ptr(out.parent_hash), int(flags), self._stream()), "arcle_expand_rows")
+        return out
 
     def get_plane(self, name, out=None):
         """One key of the state dict as a dense [N, H, W] int8 array (device tensor, or a pinned host tensor passed as `out`):

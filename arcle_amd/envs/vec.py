@@ -568,6 +568,31 @@ class ARCVecEnv:
         rows_out, reward, term = b.transition_rows(rows, form, pay, op, src_env, out, flags=fl)
         return rows_out[:, :b.state_row_size()], reward, term.view(torch.bool)
 
+    def hash_rows(self, rows):
+        """(state_hash, grid_hash) of every state row: int64 [M, 2] (see EnvBatch.hash_rows; the formula is in include/arcle_hip.h)."""
+        return self.batch.hash_rows(rows)
+
+    def expand(self, rows, action, src_env=None):
+        """K candidate actions per state row WITHOUT materialising the children — what a search does at every node.  rows int8 [M, L];
+        action = {"bbox": int32 [K,4] | "point": int32 [K,2], "operation": int32 [K]} (one action set for every row) or [M,K,..] /
+        [M,K] (a set per row); src_env as in `transition`.  Returns an Expansion of [M, K, ...] device tensors: reward, term, status
+        (ARCLE_ST_* bits of the child; such a child is its parent), hash int64 [M,K,2] = (state_hash, grid_hash) of the child state,
+        dense int32 [M,K,2] = (correct, total) cells against the answer, parent_hash [M,2] — each equal to what `transition` + `hash_rows`
+        give for that (row, action) pair.  This env's own state, status and counters are not touched."""
+        if self._host_slots:
+            raise NotImplementedError("expand needs a device-only op table (no host callables)")
+        if "bbox" in action:
+            form, pay = "bbox", action["bbox"].to(device=self.device, dtype=torch.int32).contiguous()
+        elif "point" in action:
+            form, pay = "point", action["point"].to(device=self.device, dtype=torch.int32).contiguous()
+        else:
+            raise ValueError("expand takes bbox or point actions")
+        op = action["operation"].to(device=self.device, dtype=torch.int32).contiguous()
+        if src_env is not None:
+            src_env = src_env.to(device=self.device, dtype=torch.int32).contiguous()
+        fl = STEP_RESET_ON_SUBMIT if self.flags & STEP_RESET_ON_SUBMIT else 0
+        return self.batch.expand_rows(rows, form, pay, op, src_env, dense=True, flags=fl)
+
     def autotune(self, payload, operation=None, form="bbox"):
         """Times every launch plan the library has for this env's steps (self-ordering or not, the cache policies of the speculative grid
         request, 4- or 8-wave workgroups) on K consecutive action batches of the caller — payload [K, N, ...], operation [K, N], device

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ARCLE_ABI_VERSION 6
+#define ARCLE_ABI_VERSION 7
 #define ARCLE_MAX_OPS 64
 #define ARCLE_MAX_CELLS 1024 /* H*W <= 1024: one 64-lane wavefront x 16 cells holds a plane (the one-wavefront-per-env kernels);
                                 larger planes (H, W <= 127) are served by the workgroup-per-env kernels — see "Grids beyond
@@ -447,6 +447,38 @@ int arcle_set_state_rows(arcle_env* env, const int8_t* rows, int32_t stride, con
 int arcle_transition_rows(arcle_env* env, int32_t n_rows, const int8_t* rows_in, int32_t in_stride, int ingress, const void* sel,
                           const int32_t* op, const int32_t* src_env, int8_t* rows_out, int32_t out_stride, int tail,
                           int32_t* reward, uint8_t* term, uint32_t flags, void* stream);
+/* ---- search on state rows: a state hash, and K candidate actions per row ----------------------------------------------------------
+ * hash [r][2] = (state_hash, grid_hash) of state row r.  state_hash is a function of the CONTENT of the row alone (every plane and
+ * scalar field the env kind's row carries; not of its address, alignment, stride, padding, env or answer); grid_hash covers `grid`
+ * and `grid_dim` only.  The formula (uint32 arithmetic, wrapping), with the finalisers
+ *     fa(x): x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13; x *= 0xc2b2ae35; x ^= x >> 16
+ *     fb(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ * and a term pair  T(d, t) = (fa(d ^ (t * 0x9E3779B1)), fb(d + t * 0x85EBCA77))  of a dword d under the tag t:
+ *     plane term(pl)  = sum over j < ceil(H*W / 4) of T(little-endian dword j of the plane's H*W bytes, zero-extended; (pl + 1) * 256 + j)
+ *     record term     = sum over i < 4 of T(dword i of the 16-byte record with every byte the row does not carry — answer_dim, and
+ *                       the fields the env kind lacks — set to zero; 0x0F00 + i)
+ *     (A, B)          = sum of the terms of every plane of the row (pl = enum arcle_plane) + the record term
+ *     state_hash      = A | B << 32
+ *     grid_hash       = the same from plane term(ARCLE_PL_GRID) + T(record dword 0 with the input_dim bytes zeroed, 0x0E00)
+ * Each (dword, plane, position) passes a nonlinear finaliser before the sum, so equal changes at two positions do not cancel; the sum
+ * makes the hash decomposable by plane (a child's hash = the parent's with the terms of the changed planes and the record replaced).
+ * arcle_amd/search.py::hash_rows_numpy is the same formula in NumPy.  One wavefront per row, any row alignment, stride >= the row length.
+ *
+ * arcle_expand_rows: K = n_actions candidate actions per state row, nothing but verdicts written.  rows [n_rows] are read only.
+ * Actions: ARCLE_INGRESS_BBOX (sel int32 [..][4]) or ARCLE_INGRESS_POINT (int32 [..][2]) with op int32 [..]; action_row_stride = 0:
+ * ONE set of K actions applied to every row ([K] arrays), = n_actions: a set per row ([n_rows][K]).  Mask ingress is not served
+ * here (ARCLE_ERR_ARG).  Outputs, all [n_rows][K], child c = m * K + k: reward int32, term uint8, status uint8 (the ARCLE_ST_* bits
+ * child c raised), hash uint64 [..][2], optional dense int32 [..][2] (non-NULL implies ARCLE_STEP_DENSE: correct cells, total cells
+ * of the child's grid against the answer of env src_env[m]), optional parent_hash uint64 [n_rows][2].  flags: ARCLE_STEP_RESET_ON_SUBMIT
+ * | _DENSE.  For every (m, k) the outputs equal what arcle_transition_rows reports for (row m, action (m, k), src_env[m], same flags)
+ * — reward, terminated, the tail's status byte, the dense pair — and hash equals arcle_hash_rows of the row that call would have
+ * written.  No child row is written anywhere, and the handle's sticky status word, resident envs, counters, dense cache and installed
+ * outputs are not touched.  Handles of more than ARCLE_MAX_CELLS cells per plane: ARCLE_ERR_CONFIG.  Allocates nothing: may be captured. */
+int arcle_hash_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, uint64_t* hash, void* stream);
+int arcle_expand_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t n_actions, int ingress,
+                      const void* sel, const int32_t* op, int32_t action_row_stride, const int32_t* src_env, int32_t* reward,
+                      uint8_t* term, uint8_t* status, uint64_t* hash, int32_t* dense, uint64_t* parent_hash, uint32_t flags,
+                      void* stream);
 /* One state plane as a dense [n_envs][H*W] int8 array (device or pinned host memory), a strided copy on the stream: the
  * get_state()/set_state() of single keys of the reference's state dict. */
 int arcle_get_plane(arcle_env* env, int plane, int8_t* dst, void* stream);
