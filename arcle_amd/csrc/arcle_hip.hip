@@ -593,6 +593,29 @@ struct LaunchPlan {  // how a step launch runs (see plan_launch)
   int grouped;  // 1: a launch that orders itself (ARCLE_STEPX_GROUPED)
 };
 
+// Everything about ONE launch that is not a durable property of the handle.  Entry points that need a launch to differ from what the setters
+// installed (a rollout's slice t of its outputs, arcle_autotune's scratch rows and candidate plan, arcle_step_many's record prefetch) say so
+// here; the handle itself is never edited for a launch.
+struct StepCall {
+  int ingress;
+  const void* sel;
+  const int32_t* op;
+  int32_t* reward;
+  uint8_t* term;
+  uint32_t flags;
+  uint8_t* trunc;           // destinations: ARCLE_STEP_TRUNCATE, _DENSE, _FLAT_OBS (rows + their shape), _PACK_OBS
+  int32_t* dense;
+  int8_t* flat_out;
+  int32_t flat_stride;
+  int flat_filtered, flat_tail, flat_seq;
+  int8_t* pack_out;
+  uint32_t* acct;           // the handle's byte counters (launches over its resident envs)
+  const int32_t* next_sel;  // arcle_step_many: the next step's host records / the staging buffer the front workgroups fill
+  int32_t* stage_out;
+  int in_step_many;         // ... inside such a run (its first and last launches read records no front workgroup staged)
+  const LaunchPlan* plan;   // arcle_autotune timing a candidate: the plan to launch with, in place of the tuned one or the tables
+};
+
 struct arcle_env {
   int big;  // H * W > ARCLE_MAX_CELLS: every launch of this handle goes to the workgroup-per-env kernels of arcle_big.hip
   int8_t* big_scratch;      // ... arcle_transition_rows of such a handle: scratch envs (planes, records, counters) for big_scratch_rows rows
@@ -614,9 +637,6 @@ struct arcle_env {
   uint32_t* retired_ops[64];  // op tables replaced by arcle_set_op_table: launches in flight (and captured graphs) may still read them
   int n_retired;
   int32_t* d_stage;           // int32 [2][n_envs][5]: staging of host-resident action records (arcle_step_many), allocated on first use
-  const int32_t* pf_next;     // set by arcle_step_many around a launch: the next step's host records / the staging buffer to fill
-  int32_t* pf_stage;
-  int pf_active;              // ... inside such a call (its first and last launches read records no front workgroup staged)
   int order_enabled;          // arcle_set_dispatch_order (default 1): launches of the standard batch order themselves (see the kernel)
   int stream_min;             // batches of at least this many envs take the streaming instantiations (ARCLE_STREAM_MIN_ENVS / env override)
   int spec_small_max;         // batches of at most this many envs request the grid plane speculatively (ARCLE_SPEC_SMALL_MAX env override)
@@ -624,7 +644,6 @@ struct arcle_env {
   int group_enabled;          // tuning runs: ARCLE_GROUPED = 0 switches the self-ordering launches off for handles created under it
   int group_min, group_max;   // ... for batches of group_min .. group_max envs (ARCLE_GROUP_MIN / ARCLE_GROUP_MAX)
   int group_wpw;              // ... in workgroups of this many waves (ARCLE_GROUP_WPW)
-  const LaunchPlan* forced;   // arcle_autotune timing a candidate
   int tuned_valid, tuned_ingress;   // arcle_autotune's choice for (ingress, flags) launches of this handle
   uint32_t tuned_flags;
   LaunchPlan tuned;
@@ -656,6 +675,63 @@ struct arcle_env {
 static int fail(arcle_env* e, int code, const char* msg) {
   if (e) snprintf(e->err, sizeof(e->err), "%s", msg);
   return code;
+}
+
+static bool is_capturing(void* stream) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) return false;
+  (void)hipGetLastError();
+  return true;
+}
+
+static dim3 grid_for(int n_envs, int waves_per_wg = WAVES_PER_WG) {
+  unsigned nb = (unsigned)((n_envs + waves_per_wg - 1) / waves_per_wg);
+  nb = (nb + 7u) & ~7u;
+  return dim3(nb);
+}
+
+// bytes of one step's selection payload / op array for the whole batch (arcle_step_many strides)
+static size_t payload_bytes(const arcle_env* e, int ingress) {
+  const size_t n = (size_t)e->cfg.n_envs;
+  switch (ingress) {
+    case arcle::INGRESS_MASK: return n * (size_t)e->base.P;
+    case arcle::INGRESS_BBOX: return n * 16;
+    case arcle::INGRESS_POINT: return n * 8;
+    case arcle::INGRESS_BBOX5: return n * 20;
+    default: return n * (size_t)(e->big ? e->base.PS >> 3 : ARCLE_BITS_STRIDE);
+  }
+}
+
+// ---- prerequisites several entry points share: one text each.  Every entry point applies the ones it has in its own order (where a call is
+// wrong in two ways, which fault is reported is part of the ABI's behaviour) ----
+static int need_op_table(arcle_env* e) {
+  return e->base.n_ops > 0 ? ARCLE_OK : fail(e, ARCLE_ERR_CONFIG, "no op table installed (arcle_set_op_table)");
+}
+static int need_task_table(arcle_env* e) {
+  return e->base.n_tasks > 0 ? ARCLE_OK : fail(e, ARCLE_ERR_CONFIG, "no task table installed (arcle_set_task_table)");
+}
+static int need_sampler(arcle_env* e, uint32_t flags) {
+  return !(flags & ARCLE_STEP_RESAMPLE) || e->base.n_problems > 0 ? ARCLE_OK : fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_RESAMPLE without arcle_set_sampler");
+}
+static int need_rule_planes(arcle_env* e, int ingress, uint32_t flags) {  // (the rule compares the mask with `selected`)
+  if ((flags & ARCLE_STEP_CONTINUE_RULE) && (!arcle::is_cells(ingress) || !e->bufs.plane[ARCLE_PL_SELECTED]))
+    return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_CONTINUE_RULE needs mask ingress and the `selected` plane");
+  return ARCLE_OK;
+}
+static int need_rule_mask(arcle_env* e, int ingress, uint32_t flags) {  // (the row kernels: no `selected` plane to ask for, rows carry it)
+  return (flags & ARCLE_STEP_CONTINUE_RULE) && ingress != arcle::INGRESS_MASK ? fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_CONTINUE_RULE needs mask ingress") : ARCLE_OK;
+}
+static int need_steps(arcle_env* e, int32_t n_steps) { return n_steps > 0 ? ARCLE_OK : fail(e, ARCLE_ERR_ARG, "n_steps must be positive"); }
+static int need_src_env(arcle_env* e, int32_t n_rows, const int32_t* src_env) {
+  return src_env || n_rows <= e->cfg.n_envs ? ARCLE_OK : fail(e, ARCLE_ERR_ARG, "more rows than envs: pass src_env (which env's answer every row uses)");
+}
+static int check_packed(arcle_env* e, const void* rows) {
+  return (reinterpret_cast<uintptr_t>(rows) & 15) ? fail(e, ARCLE_ERR_ARG, "packed observation rows must be 16-byte aligned") : ARCLE_OK;
+}
+// (stream-ordered) every env's dense pair becomes "unknown": whatever moves grids without keeping the pairs calls this first
+static int drop_dense_cache(arcle_env* e, void* stream) {
+  if (e->d_dense_cache) HIP_TRY(e, hipMemsetAsync(e->d_dense_cache, 0, (size_t)e->cfg.n_envs * 8, (hipStream_t)stream));
+  return ARCLE_OK;
 }
 
 extern "C" int arcle_abi_version(void) { return ARCLE_ABI_VERSION; }
@@ -847,6 +923,64 @@ static int big_done(arcle_env* e, int hip_rc, const char* what) {
   }
   return ARCLE_OK;
 }
+
+// ---- the launch request -> kernel arguments ---------------------------------------------------------------------------------------------
+// a request with the action arrays and nothing else: no outputs beyond reward / term, no accounting
+static StepCall action_call(int ingress, const void* sel, const int32_t* op, int32_t* reward, uint8_t* term, uint32_t flags) {
+  return StepCall{ingress, sel, op, reward, term, flags};  // (the rest zero)
+}
+// ... with the destinations the setters installed: the one place that reads them for a launch
+static StepCall from_handle(const arcle_env* e, int ingress, const void* sel, const int32_t* op, int32_t* reward, uint8_t* term, uint32_t flags) {
+  StepCall c = action_call(ingress, sel, op, reward, term, flags);
+  c.trunc = e->base.trunc;
+  c.dense = e->base.dense;
+  c.flat_out = e->flat_out;
+  c.flat_stride = e->flat_stride;
+  c.flat_filtered = e->flat_filtered;
+  c.flat_tail = e->flat_tail;
+  c.flat_seq = e->flat_seq;
+  c.pack_out = e->pack_out;
+  c.acct = e->d_acct;
+  return c;
+}
+// the rows of a request (StepParams and BigParams name the fields alike)
+template <class P>
+static void fill_rows(P& p, const StepCall& c) {
+  p.flat_out = c.flat_out;
+  p.flat_stride = c.flat_stride;
+  p.flat_filter = c.flat_filtered ? 1 : 0;
+  p.flat_tail = c.flat_tail ? 1 : 0;
+  p.flat_seq = c.flat_tail ? c.flat_seq : 0;
+}
+// the per-launch part of a kernel argument block; row destinations only where the flags ask for them
+template <class P>
+static void fill_call(P& p, const StepCall& c) {
+  p.ingress = c.ingress;
+  p.sel = c.sel;
+  p.op = c.op;
+  p.reward = c.reward;
+  p.term = c.term;
+  p.flags = c.flags;
+  p.trunc = c.trunc;
+  p.dense = c.dense;
+  p.acct = c.acct;
+  p.rmask = nullptr;
+  if (c.flags & ARCLE_STEP_FLAT_OBS) fill_rows(p, c);
+  if (c.flags & ARCLE_STEP_PACK_OBS) p.pack_out = reinterpret_cast<decltype(p.pack_out)>(c.pack_out);
+}
+static StepParams make_params(const arcle_env* e, const StepCall& c) {
+  StepParams p = e->base;
+  fill_call(p, c);
+  p.next_sel = c.next_sel;
+  p.stage_out = c.stage_out;
+  return p;
+}
+static arcle_big::BigParams make_big_params(const arcle_env* e, const StepCall& c) {
+  arcle_big::BigParams q = big_params(e);
+  fill_call(q, c);
+  return q;
+}
+
 extern "C" int arcle_set_op_table(arcle_env* e, const uint32_t* descs, int32_t n_ops) {
   if (!e || !descs) return ARCLE_ERR_ARG;
   DeviceGuard guard(e->device);
@@ -933,48 +1067,36 @@ extern "C" int arcle_can_elide_selected(const arcle_env* e) {
   return e->bufs.plane[ARCLE_PL_SELECTED] != nullptr;
 }
 
-static dim3 grid_for(int n_envs, int waves_per_wg = WAVES_PER_WG);
-
-extern "C" int arcle_reset_from_table(arcle_env* e, const int32_t* task_idx, const uint8_t* mask, void* stream) {
-  if (!e || !task_idx) return ARCLE_ERR_ARG;
+// reset() of the masked envs (mask NULL = all).  mode 0: onto the tasks their planes hold; 1: from the task table by task_idx, with an explicit
+// augmentation where given; 2: onto device-drawn tasks (arcle_set_sampler)
+static int launch_reset(arcle_env* e, int mode, const uint8_t* mask, const int32_t* task_idx, const uint8_t* aug_k, const uint8_t* aug_perm,
+                        const char* what, void* stream) {
   DeviceGuard guard(e->device);
-  if (e->base.n_tasks <= 0) return fail(e, ARCLE_ERR_CONFIG, "no task table installed (arcle_set_task_table)");
-  if (e->big) {
-    arcle_big::BigParams q = big_params(e);
-    q.rmask = mask;
-    q.task_idx = task_idx;
-    return big_done(e, arcle_big::launch_reset(q, 1, stream), "arcle_reset_from_table");
-  }
-  StepParams p = e->base;
-  p.rmask = mask;
-  p.task_idx = task_idx;
-  hipLaunchKernelGGL(arcle_reset_table_kernel, grid_for(p.n_envs), dim3(64 * WAVES_PER_WG), 0, (hipStream_t)stream, p);
+  auto fill = [&](auto p) {
+    p.rmask = mask;
+    p.task_idx = task_idx;
+    p.aug_k = aug_k;
+    p.aug_perm = aug_perm;
+    return p;
+  };
+  if (e->big) return big_done(e, arcle_big::launch_reset(fill(big_params(e)), mode, stream), what);
+  const StepParams p = fill(e->base);
+  if (mode == 0) hipLaunchKernelGGL(arcle_reset_kernel, grid_for(p.n_envs), dim3(64 * WAVES_PER_WG), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(arcle_reset_table_kernel, grid_for(p.n_envs), dim3(64 * WAVES_PER_WG), 0, (hipStream_t)stream, p);
   HIP_TRY(e, hipGetLastError());
   return ARCLE_OK;
-}
-
-static dim3 grid_for(int n_envs, int waves_per_wg) {
-  unsigned nb = (unsigned)((n_envs + waves_per_wg - 1) / waves_per_wg);
-  nb = (nb + 7u) & ~7u;
-  return dim3(nb);
 }
 
 extern "C" int arcle_reset(arcle_env* e, const uint8_t* mask, void* stream) {
   if (!e) return ARCLE_ERR_ARG;
-  DeviceGuard guard(e->device);
-  if (e->big) {
-    arcle_big::BigParams q = big_params(e);
-    q.rmask = mask;
-    return big_done(e, arcle_big::launch_reset(q, 0, stream), "arcle_reset");
-  }
-  StepParams p = e->base;
-  p.rmask = mask;
-  hipLaunchKernelGGL(arcle_reset_kernel, grid_for(p.n_envs), dim3(64 * WAVES_PER_WG), 0, (hipStream_t)stream, p);
-  HIP_TRY(e, hipGetLastError());
-  return ARCLE_OK;
+  return launch_reset(e, 0, mask, nullptr, nullptr, nullptr, "arcle_reset", stream);
 }
 
-static int launch_flatten(arcle_env* e, int8_t* out, int32_t out_stride, int filtered, hipStream_t st);
+extern "C" int arcle_reset_from_table(arcle_env* e, const int32_t* task_idx, const uint8_t* mask, void* stream) {
+  if (!e || !task_idx) return ARCLE_ERR_ARG;
+  if (int rc = need_task_table(e)) return rc;
+  return launch_reset(e, 1, mask, task_idx, nullptr, nullptr, "arcle_reset_from_table", stream);
+}
 
 // ---- instantiation dispatch: (ingress, width class, flags, accounting) -> kernel --------------------------------------
 static int width_class(const StepParams& p) {
@@ -1112,12 +1234,30 @@ static int launch_step_tbl(bool acct, bool feat, dim3 g, dim3 b, hipStream_t st,
     return launch_step_kernel<ING, FW, 0, 0>(g, b, st, p), ARCLE_OK;
   }
 }
-template <int ING>
-static int launch_step_ing(int fw, bool acct, bool feat, dim3 g, dim3 b, hipStream_t st, const StepParams& p) {
-  if (fw == arcle::FW_FULL) return launch_step_tbl<ING, arcle::FW_FULL>(acct, feat, g, b, st, p);
-  if (fw == arcle::FW_FAST) return launch_step_tbl<ING, arcle::FW_FAST>(acct, feat, g, b, st, p);
-  return launch_step_tbl<ING, arcle::FW_GENERIC>(acct, feat, g, b, st, p);
+// Run-time (ingress, width class) -> compile-time <ING, FW>: calls f(ing, fw) with two integral constants and returns what it returns.
+// FORMS: the ingress forms the caller takes (bits 1 << ING, as in the LEAN table); a form outside it: ARCLE_ERR_ARG, f is not called (takes()
+// is the same question for the caller's argument check).  FULL: the caller's kernels have FW_FULL instantiations of their own (the step
+// kernels); those that keep the planes in registers have not — lane predication does not matter there, FW_FULL shares FW_FAST's code.
+static constexpr bool takes(uint32_t forms, int ingress) { return ingress >= 0 && ingress <= arcle::INGRESS_BITS && ((forms >> ingress) & 1u); }
+static constexpr uint32_t ROW_FORMS = I_MASK | I_BBOX | I_POINT;  // rollouts, arcle_transition_rows
+template <uint32_t FORMS, bool FULL, int ING = 0, class F>
+static int with_form(int ingress, int fw, F&& f) {
+  if constexpr (ING > arcle::INGRESS_BITS) return ARCLE_ERR_ARG;
+  else {
+    if constexpr (takes(FORMS, ING)) {
+      if (ingress == ING) {
+        using I = std::integral_constant<int, ING>;
+        if constexpr (FULL) {
+          if (fw == arcle::FW_FULL) return f(I(), std::integral_constant<int, arcle::FW_FULL>());
+        }
+        if (fw != arcle::FW_GENERIC) return f(I(), std::integral_constant<int, arcle::FW_FAST>());
+        return f(I(), std::integral_constant<int, arcle::FW_GENERIC>());
+      }
+    }
+    return with_form<FORMS, FULL, ING + 1>(ingress, fw, f);
+  }
 }
+static int bad_ingress(arcle_env* e) { return fail(e, ARCLE_ERR_ARG, "unknown ingress form"); }
 
 // ... and whether a launch of this handle with these parameters (flags, row shape already filled in) CAN take it (whether it does: plan_launch)
 static bool grouped_applies(const arcle_env* e, int ingress, const StepParams& p) {
@@ -1175,17 +1315,19 @@ static int launch_wpw(const arcle_env* e) {
 // How a step launch of this handle runs: cache policy of the speculative grid request, workgroup size, self-ordering or not.  The library's
 // tables (stream_policy, launch_wpw, the grouping window) were measured on one box with one action-stream regime; arcle_autotune replaces
 // them, per handle, by what it measured on THIS handle's size, box and action residency.
-// p: the launch's parameters with flags and row shape filled in; device_payload: the actions live in device memory
-static LaunchPlan plan_launch(const arcle_env* e, int ingress, const StepParams& p, bool device_payload) {
+// c: the request (a candidate plan, the record prefetch of arcle_step_many); p: the parameters built from it, with the flags the launch really runs
+// with; device_payload: the actions live in device memory
+static LaunchPlan plan_launch(const arcle_env* e, const StepCall& c, const StepParams& p, bool device_payload) {
   const uint32_t flags = p.flags;
+  const int ingress = c.ingress;
   const bool std30 = p.H == 30 && p.W == 30 && p.PS == ARCLE_MAX_CELLS;
   // which choices exist for this launch at all
-  const bool can_group = device_payload && !e->pf_active && grouped_applies(e, ingress, p);
+  const bool can_group = device_payload && !c.in_step_many && grouped_applies(e, ingress, p);
   const bool any_policy = std30 && lean_twin(TW_STREAM, ingress, p);                            // the lean streaming instantiations
   const bool policy_a = !std30 && !(flags & ARCLE_STEP_FEATURE_FLAGS) && ingress != arcle::INGRESS_MASK;  // other shapes: the run-time request
   LaunchPlan pl;
-  if (e->forced) {  // (arcle_autotune timing a candidate)
-    pl = *e->forced;
+  if (c.plan) {  // (arcle_autotune timing a candidate)
+    pl = *c.plan;
   } else if (e->tuned_valid && e->tuned_ingress == ingress && e->tuned_flags == flags) {
     pl = e->tuned;
   } else {
@@ -1193,10 +1335,10 @@ static LaunchPlan plan_launch(const arcle_env* e, int ingress, const StepParams&
     pl.wpw = launch_wpw(e);
     // ... and for a batch of at most one occupancy round whose launch has no front workgroups to carry (no records to prefetch): 5.40 -> 5.35 us
     // at 8192 envs, 4.28 -> 4.25 at 4096; from 16384 envs on 8 waves are the better shape (profiles/round4_experiments.txt §9)
-    if (!e->wpw_override && pl.wpw == WAVES_PER_WG && p.n_envs <= 8192 && !e->pf_next) pl.wpw = 4;
+    if (!e->wpw_override && pl.wpw == WAVES_PER_WG && p.n_envs <= 8192 && !c.next_sel) pl.wpw = 4;
     // ... round 5, the lean bbox / record kernel between 8192 and 65536 envs as well: 4-wave workgroups 2-4 % ahead of 8 at 12 288 … 49 152
     // envs whatever the policy (profiles/round5_experiments.txt §4c: e.g. 32 768 envs plain 13.2 vs 13.7 us, 40 960 B 17.4 vs 17.6)
-    if (!e->wpw_override && any_policy && !e->pf_next) pl.wpw = 4;
+    if (!e->wpw_override && any_policy && !c.next_sel) pl.wpw = 4;
     // self-ordering launches inside the window they were measured to win in with a cache-resident action stream (profiles/round5_experiments.txt)
     pl.grouped = p.n_envs >= e->group_min && p.n_envs <= e->group_max;
     if (pl.grouped && can_group && !e->wpw_override) pl.wpw = e->group_wpw;
@@ -1204,7 +1346,7 @@ static LaunchPlan plan_launch(const arcle_env* e, int ingress, const StepParams&
   if (!can_group) pl.grouped = 0;
   if (pl.grouped) pl.policy = 0;
   else if (!(any_policy || (policy_a && pl.policy == 'A'))) pl.policy = 0;
-  if (e->pf_next && pl.wpw != WAVES_PER_WG) pl.wpw = WAVES_PER_WG;  // (the record-prefetching launch is written for 8-wave workgroups)
+  if (c.next_sel && pl.wpw != WAVES_PER_WG) pl.wpw = WAVES_PER_WG;  // (the record-prefetching launch is written for 8-wave workgroups)
   if (pl.wpw & (pl.wpw - 1)) pl.grouped = 0;  // (a self-ordering launch rebuilds its slot from log2 of the workgroup's waves: powers of two only)
   return pl;
 }
@@ -1216,140 +1358,84 @@ static uint32_t effective_flags(const arcle_env* e, uint32_t flags) {
   return flags;
 }
 
-static int launch_step(arcle_env* e, int ingress, const void* sel, const int32_t* op, int32_t* reward, uint8_t* term,
-                       uint32_t flags, void* stream) {
-  if (!e || !sel || (!op && ingress != arcle::INGRESS_BBOX5) || !reward || !term) return ARCLE_ERR_ARG;
-  if (e->base.n_ops <= 0) return fail(e, ARCLE_ERR_CONFIG, "no op table installed (arcle_set_op_table)");
-  if ((flags & ARCLE_STEP_TRUNCATE) && !e->base.trunc) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_TRUNCATE without arcle_set_truncation");
-  if ((flags & ARCLE_STEP_RESAMPLE) && e->base.n_problems <= 0) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_RESAMPLE without arcle_set_sampler");
-  if ((flags & ARCLE_STEP_DENSE) && (!e->base.dense || !e->bufs.plane[ARCLE_PL_ANSWER])) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_DENSE without arcle_set_dense_output");
-  if ((flags & ARCLE_STEP_CONTINUE_RULE) && (!arcle::is_cells(ingress) || !e->bufs.plane[ARCLE_PL_SELECTED]))
-    return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_CONTINUE_RULE needs mask ingress and the `selected` plane");
-  if (flags & ~0x3ffu) return fail(e, ARCLE_ERR_ARG, "unknown step flag");
-  if ((flags & ARCLE_STEP_ROWS_INCREMENTAL) && !(flags & ARCLE_STEP_FLAT_OBS)) return fail(e, ARCLE_ERR_ARG, "ARCLE_STEP_ROWS_INCREMENTAL without ARCLE_STEP_FLAT_OBS");
+static int launch_step(arcle_env* e, const StepCall& c, void* stream) {
+  const int ingress = c.ingress;
+  if (!c.sel || (!c.op && ingress != arcle::INGRESS_BBOX5) || !c.reward || !c.term) return ARCLE_ERR_ARG;
+  if (int rc = need_op_table(e)) return rc;
+  if ((c.flags & ARCLE_STEP_TRUNCATE) && !c.trunc) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_TRUNCATE without arcle_set_truncation");
+  if (int rc = need_sampler(e, c.flags)) return rc;
+  if ((c.flags & ARCLE_STEP_DENSE) && (!c.dense || !e->bufs.plane[ARCLE_PL_ANSWER])) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_DENSE without arcle_set_dense_output");
+  if (int rc = need_rule_planes(e, ingress, c.flags)) return rc;
+  if (c.flags & ~0x3ffu) return fail(e, ARCLE_ERR_ARG, "unknown step flag");
+  if ((c.flags & ARCLE_STEP_ROWS_INCREMENTAL) && !(c.flags & ARCLE_STEP_FLAT_OBS)) return fail(e, ARCLE_ERR_ARG, "ARCLE_STEP_ROWS_INCREMENTAL without ARCLE_STEP_FLAT_OBS");
+  if ((c.flags & ARCLE_STEP_FLAT_OBS) && !c.flat_out) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_FLAT_OBS without arcle_set_flat_output");
+  if ((c.flags & ARCLE_STEP_PACK_OBS) && !c.pack_out) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_PACK_OBS without arcle_set_packed_output");
+  if (!takes(I_ANY, ingress)) return bad_ingress(e);
   DeviceGuard guard(e->device);
   if (e->big) {
     // one workgroup per env (arcle_big.hip).  Flags: AUTORESET, ELIDE_SELECTED, TRUNCATE, RESAMPLE (without augmentation), CONTINUE_RULE,
     // RESET_ON_SUBMIT, FLAT_OBS (+ tail / completion signal), PACK_OBS; ROWS_INCREMENTAL rewrites the rows in full (identical bytes)
-    arcle_big::BigParams q = big_params(e);
-    q.ingress = ingress;
-    q.sel = sel;
-    q.op = op;
-    q.reward = reward;
-    q.term = term;
-    q.flags = flags;
-    q.dense = e->base.dense;
-    q.acct = e->d_acct;
-    if (e->d_acct) e->acct_steps += (uint64_t)q.n_envs;
-    if (flags & ARCLE_STEP_FLAT_OBS) {
-      if (!e->flat_out) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_FLAT_OBS without arcle_set_flat_output");
-      q.flat_out = e->flat_out;
-      q.flat_stride = e->flat_stride;
-      q.flat_filter = e->flat_filtered ? 1 : 0;
-      q.flat_tail = e->flat_tail ? 1 : 0;
-      q.flat_seq = e->flat_tail ? e->flat_seq : 0;
-    }
-    if (flags & ARCLE_STEP_PACK_OBS) {
-      if (!e->pack_out) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_PACK_OBS without arcle_set_packed_output");
-      q.pack_out = reinterpret_cast<uint8_t*>(e->pack_out);
-    }
-    return big_done(e, arcle_big::launch_step(q, stream), "arcle_step");
+    if (e->d_acct) e->acct_steps += (uint64_t)e->cfg.n_envs;
+    return big_done(e, arcle_big::launch_step(make_big_params(e, c), stream), "arcle_step");
   }
   // A step without ARCLE_STEP_DENSE on a handle that keeps dense pairs may move grids the cache still describes: drop the entries first
   // (stream-ordered; handles that always step with the flag never get here).  Only needed while the cache may hold pairs: a host flag,
   // set by dense steps — and stuck at "always" once a dense step was captured into a hipGraph, whose replays fill the cache unseen.
   if (e->d_dense_cache) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-    if (flags & ARCLE_STEP_DENSE) {
+    const bool capturing = is_capturing(stream);
+    if (c.flags & ARCLE_STEP_DENSE) {
       e->dense_cache_live = capturing ? 2 : (e->dense_cache_live == 2 ? 2 : 1);
     } else if (capturing || e->dense_cache_live) {
-      HIP_TRY(e, hipMemsetAsync(e->d_dense_cache, 0, (size_t)e->cfg.n_envs * 8, (hipStream_t)stream));
+      if (int rc = drop_dense_cache(e, stream)) return rc;
       if (!capturing && e->dense_cache_live == 1) e->dense_cache_live = 0;
     }
   }
+  StepParams p = make_params(e, c);
   // env kinds without a `selected` plane (ARCEnv, RawARCEnv: no table of theirs can hold a reset_sel-wrapped op — arcle_set_op_table
   // rejects it): the zero-fill elision is vacuous there, so an auto-resetting step of such a handle takes the same lean instantiations
   // as the O2ARC batch (ARCVecEnv's flag set) instead of the runtime-flag kernel
-  flags = effective_flags(e, flags);
-  StepParams p = e->base;
-  p.ingress = ingress;
-  p.sel = sel;
-  p.op = op;
-  p.reward = reward;
-  p.term = term;
-  p.flags = flags;
-  p.acct = e->d_acct;
+  p.flags = effective_flags(e, c.flags);
 #ifdef ARCLE_TRACE_WAVES
   if (!e->d_acct && e->d_trace) {
     p.acct = reinterpret_cast<uint32_t*>(e->d_trace);
     p.n_steps = e->trace_seq++;
   }
 #endif
-  p.rmask = nullptr;
-  p.next_sel = e->pf_next;
-  p.stage_out = e->pf_stage;
-  if (flags & ARCLE_STEP_FLAT_OBS) {
-    if (!e->flat_out) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_FLAT_OBS without arcle_set_flat_output");
-    p.flat_out = e->flat_out;
-    p.flat_stride = e->flat_stride;
-    p.flat_filter = e->flat_filtered ? 1 : 0;
-    p.flat_tail = e->flat_tail ? 1 : 0;
-    p.flat_seq = e->flat_tail ? e->flat_seq : 0;
-  }
-  if (flags & ARCLE_STEP_PACK_OBS) {
-    if (!e->pack_out) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_PACK_OBS without arcle_set_packed_output");
-    p.pack_out = e->pack_out;
-  }
   // (a self-ordering launch reads the actions of 32 envs per wave: only from device memory, see on_device)
-  const bool dev_payload = grouped_applies(e, ingress, p) && on_device(e, sel) && (ingress == arcle::INGRESS_BBOX5 || on_device(e, op));
-  const LaunchPlan pl = plan_launch(e, ingress, p, dev_payload);
+  const bool dev_payload = grouped_applies(e, ingress, p) && on_device(e, c.sel) && (ingress == arcle::INGRESS_BBOX5 || on_device(e, c.op));
+  const LaunchPlan pl = plan_launch(e, c, p, dev_payload);
   p.spec_grid = pl.policy;
   p.wpw = pl.wpw;
   p.group_magic = pl.grouped ? (uint32_t)(0x100000000ull / (uint64_t)(p.n_envs / (8 * ARCLE_GROUP_SIZE))) + 1u : 0u;  // (G = groups per XCD >= 2)
   const dim3 g = grid_for(p.n_envs, pl.wpw), b(64 * pl.wpw);
-  hipStream_t st = (hipStream_t)stream;
-  const int fw = width_class(p);
-  const bool acct = e->d_acct != nullptr;
-  const bool feat = (flags & ARCLE_STEP_FEATURE_FLAGS) != 0;
-  int rc;
-  switch (ingress) {
-    case arcle::INGRESS_BBOX: rc = launch_step_ing<arcle::INGRESS_BBOX>(fw, acct, feat, g, b, st, p); break;
-    case arcle::INGRESS_POINT: rc = launch_step_ing<arcle::INGRESS_POINT>(fw, acct, feat, g, b, st, p); break;
-    case arcle::INGRESS_MASK: rc = launch_step_ing<arcle::INGRESS_MASK>(fw, acct, feat, g, b, st, p); break;
-    case arcle::INGRESS_BBOX5: rc = launch_step_ing<arcle::INGRESS_BBOX5>(fw, acct, feat, g, b, st, p); break;
-    case arcle::INGRESS_BITS: rc = launch_step_ing<arcle::INGRESS_BITS>(fw, acct, feat, g, b, st, p); break;
-    default: return fail(e, ARCLE_ERR_ARG, "unknown ingress form");
-  }
+  const bool acct = e->d_acct != nullptr, feat = (p.flags & ARCLE_STEP_FEATURE_FLAGS) != 0;
+  const int rc = with_form<I_ANY, true>(ingress, width_class(p), [&](auto ing, auto fw) {
+    return launch_step_tbl<decltype(ing)::value, decltype(fw)::value>(acct, feat, g, b, (hipStream_t)stream, p);
+  });
   if (rc != ARCLE_OK) return fail(e, rc, "this build of libarcle_hip has no kernel for the configuration");
   HIP_TRY(e, hipGetLastError());
   if (e->d_acct) e->acct_steps += (uint64_t)p.n_envs;
   return ARCLE_OK;
 }
-
-static size_t payload_bytes(const arcle_env* e, int ingress);
+// a step of the resident envs into the outputs the setters installed
+static int step_installed(arcle_env* e, int ingress, const void* sel, const int32_t* op, int32_t* reward, uint8_t* term, uint32_t flags, void* stream) {
+  if (!e) return ARCLE_ERR_ARG;
+  return launch_step(e, from_handle(e, ingress, sel, op, reward, term, flags), stream);
+}
 
 extern "C" int arcle_launch_info(arcle_env* e, int ingress, uint32_t flags, int32_t* out4) {
-  if (e && out4 && e->big) {  // one workgroup per env: no plan to choose; [2] = its wavefronts for this flag set / ingress form
-    arcle_big::BigParams q = big_params(e);
-    q.flags = flags;
-    q.ingress = ingress;
-    q.acct = e->d_acct;
+  if (!e || !out4) return ARCLE_ERR_ARG;
+  if (e->big) {  // one workgroup per env: no plan to choose; [2] = its wavefronts for this flag set / ingress form
     out4[0] = 0;
     out4[1] = 0;
-    out4[2] = arcle_big::step_threads(q) / 64;
+    out4[2] = arcle_big::step_threads(make_big_params(e, from_handle(e, ingress, nullptr, nullptr, nullptr, nullptr, flags))) / 64;
     out4[3] = 0;
     return ARCLE_OK;
   }
-  if (!e || !out4) return ARCLE_ERR_ARG;
-  if (ingress < 0 || ingress > arcle::INGRESS_BITS) return fail(e, ARCLE_ERR_ARG, "unknown ingress form");
+  if (!takes(I_ANY, ingress)) return bad_ingress(e);
   flags = effective_flags(e, flags);
-  StepParams p = e->base;
-  p.flags = flags;
-  p.flat_stride = e->flat_stride;
-  p.flat_filter = e->flat_filtered ? 1 : 0;
-  p.flat_tail = e->flat_tail ? 1 : 0;
-  const LaunchPlan pl = plan_launch(e, ingress, p, true);
+  const StepCall c = from_handle(e, ingress, nullptr, nullptr, nullptr, nullptr, flags);
+  const LaunchPlan pl = plan_launch(e, c, make_params(e, c), true);
   out4[0] = pl.grouped;
   out4[1] = pl.policy;
   out4[2] = pl.wpw;
@@ -1363,18 +1449,14 @@ extern "C" int arcle_launch_info(arcle_env* e, int ingress, uint32_t flags, int3
 extern "C" int arcle_autotune(arcle_env* e, int ingress, int32_t n_batches, const void* sel, const int32_t* op, uint32_t flags, int32_t* report,
                               int32_t report_rows, void* stream) {
   if (!e || !sel || (!op && ingress != arcle::INGRESS_BBOX5)) return ARCLE_ERR_ARG;
-  if (ingress < 0 || ingress > arcle::INGRESS_BITS) return fail(e, ARCLE_ERR_ARG, "unknown ingress form");
+  if (!takes(I_ANY, ingress)) return bad_ingress(e);
   if (n_batches <= 0) return fail(e, ARCLE_ERR_ARG, "arcle_autotune: n_batches must be positive");
   if (e->big) return 0;  // (no candidates: the workgroup-per-env launch has one plan)
   if (flags & ~(uint32_t)(ARCLE_STEP_AUTORESET | ARCLE_STEP_ELIDE_SELECTED | ARCLE_STEP_PACK_OBS))
     return fail(e, ARCLE_ERR_CONFIG, "arcle_autotune: ARCLE_STEP_AUTORESET | _ELIDE_SELECTED | _PACK_OBS only (other flags keep per-env side state it does not save)");
   if (e->d_acct) return fail(e, ARCLE_ERR_CONFIG, "arcle_autotune: not with byte accounting enabled");
   hipStream_t st = (hipStream_t)stream;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
-    (void)hipGetLastError();
-    return fail(e, ARCLE_ERR_CONFIG, "arcle_autotune: not inside a stream capture");
-  }
+  if (is_capturing(stream)) return fail(e, ARCLE_ERR_CONFIG, "arcle_autotune: not inside a stream capture");
   DeviceGuard guard(e->device);
   const size_t n = (size_t)e->cfg.n_envs, pbytes = n * (size_t)e->base.PS, pb = payload_bytes(e, ingress);
   // (the timed launches walk the caller's action batches in order, like arcle_step_many: ONE repeated batch is not a workload — the state
@@ -1389,17 +1471,18 @@ extern "C" int arcle_autotune(arcle_env* e, int ingress, int32_t n_batches, cons
   int8_t* save_rec = nullptr;
   int32_t *save_cnt = nullptr, *t_reward = nullptr;
   uint8_t* t_term = nullptr;
-  // (the caller's packed-row buffer and the sticky status word are part of "the handle as it was found": the timed launches write their
-  // rows to a scratch buffer, and the status word is saved and put back)
-  int8_t *t_pack = nullptr, *const caller_pack = e->pack_out;
+  // (the caller's packed-row buffer and the sticky status word are part of "the handle as it was found": the timed launches' requests name a
+  // scratch buffer for their rows, and the status word is saved and put back)
+  int8_t* t_pack = nullptr;
   uint32_t* save_status = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool ok = hipMalloc((void**)&save_rec, n * ARCLE_REC_BYTES) == hipSuccess && hipMalloc((void**)&save_cnt, n * 8) == hipSuccess &&
             hipMalloc((void**)&t_reward, n * 4) == hipSuccess && hipMalloc((void**)&t_term, n) == hipSuccess &&
             hipMalloc((void**)&save_status, 8) == hipSuccess && hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess;
-  if (ok && (flags & ARCLE_STEP_PACK_OBS) && caller_pack) {
+  StepCall c = from_handle(e, ingress, sel, op, t_reward, t_term, flags);
+  if (ok && (flags & ARCLE_STEP_PACK_OBS) && c.pack_out) {
     ok = hipMalloc((void**)&t_pack, n * (size_t)arcle_packed_obs_size(e)) == hipSuccess;
-    if (ok) e->pack_out = t_pack;
+    c.pack_out = t_pack;
   }
   ok = ok && hipMemcpyAsync(save_status, e->d_status, 8, hipMemcpyDeviceToDevice, st) == hipSuccess;
   for (int i = 0; ok && i < ARCLE_N_PLANES; i++)
@@ -1426,18 +1509,20 @@ extern "C" int arcle_autotune(arcle_env* e, int ingress, int32_t n_batches, cons
         for (int wpw = 4; wpw <= 8 && rc == ARCLE_OK; wpw += 4) {
           LaunchPlan cand = {policies[pi], wpw, grouped};
           // does the candidate survive planning unchanged?  (a policy / the grouping the launch cannot take is not a candidate)
-          StepParams probe = e->base;
+          c.plan = &cand;
+          StepParams probe = make_params(e, c);
           probe.flags = effective_flags(e, flags);
-          e->forced = &cand;
           const bool dev_payload = on_device(e, sel) && (ingress == arcle::INGRESS_BBOX5 || on_device(e, op));
-          const LaunchPlan got = plan_launch(e, ingress, probe, dev_payload);
+          const LaunchPlan got = plan_launch(e, c, probe, dev_payload);
           if (got.policy == cand.policy && got.wpw == cand.wpw && got.grouped == cand.grouped) {
             float ms = 0.f;
             bool r = copy_state(false);
             for (int it = 0; r && it < n_warm + n_timed; it++) {
               if (it == n_warm) r = hipEventRecord(ev0, st) == hipSuccess;
               const size_t bi = (size_t)(it % n_batches);
-              if (r) rc = launch_step(e, ingress, (const char*)sel + bi * pb, op ? op + bi * n : nullptr, t_reward, (uint8_t*)t_term, flags, stream);
+              c.sel = (const char*)sel + bi * pb;
+              c.op = op ? op + bi * n : nullptr;
+              if (r) rc = launch_step(e, c, stream);
               r = r && rc == ARCLE_OK;
             }
             r = r && hipEventRecord(ev1, st) == hipSuccess && hipEventSynchronize(ev1) == hipSuccess && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess;
@@ -1451,14 +1536,12 @@ extern "C" int arcle_autotune(arcle_env* e, int ingress, int32_t n_batches, cons
               }
             }
           }
-          e->forced = nullptr;
         }
     if (!copy_state(false) || hipMemcpyAsync(e->d_status, save_status, 8, hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
       rc = rc == ARCLE_OK ? ARCLE_ERR_HIP : rc;
   } else {
     rc = ARCLE_ERR_HIP;
   }
-  e->pack_out = caller_pack;
   if (t_pack) (void)hipFree(t_pack);
   if (save_status) (void)hipFree(save_status);
   for (int i = 0; i < ARCLE_N_PLANES; i++)
@@ -1485,51 +1568,38 @@ extern "C" int arcle_autotune(arcle_env* e, int ingress, int32_t n_batches, cons
 
 extern "C" int arcle_step_mask(arcle_env* e, const int8_t* sel, const int32_t* op, int32_t* reward, uint8_t* term,
                                uint32_t flags, void* stream) {
-  return launch_step(e, arcle::INGRESS_MASK, sel, op, reward, term, flags, stream);
+  return step_installed(e, arcle::INGRESS_MASK, sel, op, reward, term, flags, stream);
 }
 extern "C" int arcle_step_bbox(arcle_env* e, const int32_t* bbox, const int32_t* op, int32_t* reward, uint8_t* term,
                                uint32_t flags, void* stream) {
-  return launch_step(e, arcle::INGRESS_BBOX, bbox, op, reward, term, flags, stream);
+  return step_installed(e, arcle::INGRESS_BBOX, bbox, op, reward, term, flags, stream);
 }
 extern "C" int arcle_step_point(arcle_env* e, const int32_t* xy, const int32_t* op, int32_t* reward, uint8_t* term,
                                 uint32_t flags, void* stream) {
-  return launch_step(e, arcle::INGRESS_POINT, xy, op, reward, term, flags, stream);
+  return step_installed(e, arcle::INGRESS_POINT, xy, op, reward, term, flags, stream);
 }
 extern "C" int arcle_step_bbox5(arcle_env* e, const int32_t* act5, int32_t* reward, uint8_t* term, uint32_t flags, void* stream) {
-  return launch_step(e, arcle::INGRESS_BBOX5, act5, nullptr, reward, term, flags, stream);
+  return step_installed(e, arcle::INGRESS_BBOX5, act5, nullptr, reward, term, flags, stream);
 }
 extern "C" int arcle_step_bits(arcle_env* e, const uint8_t* bits, const int32_t* op, int32_t* reward, uint8_t* term,
                                uint32_t flags, void* stream) {
-  return launch_step(e, arcle::INGRESS_BITS, bits, op, reward, term, flags, stream);
-}
-
-// bytes of one step's selection payload / op array for the whole batch (arcle_step_many strides)
-static size_t payload_bytes(const arcle_env* e, int ingress) {
-  const size_t n = (size_t)e->cfg.n_envs;
-  switch (ingress) {
-    case arcle::INGRESS_MASK: return n * (size_t)e->base.P;
-    case arcle::INGRESS_BBOX: return n * 16;
-    case arcle::INGRESS_POINT: return n * 8;
-    case arcle::INGRESS_BBOX5: return n * 20;
-    default: return n * (size_t)(e->big ? e->base.PS >> 3 : ARCLE_BITS_STRIDE);
-  }
+  return step_installed(e, arcle::INGRESS_BITS, bits, op, reward, term, flags, stream);
 }
 
 extern "C" int arcle_step_many(arcle_env* e, int ingress, int32_t n_steps, const void* sel, const int32_t* op, int32_t* reward,
                                uint8_t* term, uint32_t flags, void* stream) {
   if (!e) return ARCLE_ERR_ARG;
-  if (n_steps <= 0) return fail(e, ARCLE_ERR_ARG, "n_steps must be positive");
-  if (ingress < 0 || ingress > arcle::INGRESS_BITS) return fail(e, ARCLE_ERR_ARG, "unknown ingress form");
-  if (n_steps == 1) return launch_step(e, ingress, sel, op, reward, term, flags, stream);
+  if (int rc = need_steps(e, n_steps)) return rc;
+  if (!takes(I_ANY, ingress)) return bad_ingress(e);
+  StepCall c = from_handle(e, ingress, sel, op, reward, term, flags);
+  if (n_steps == 1) return launch_step(e, c, stream);
   const size_t n = (size_t)e->cfg.n_envs, pb = payload_bytes(e, ingress);
   // Host-resident 5-tuple records (a policy on the CPU): step t reads its records from a device staging buffer that the FRONT
   // workgroups of launch t-1 filled from pinned host memory while that launch ran; only step 0 reads across PCIe itself.
   bool prefetch = false;
   // (only where the lean instantiation that carries the copy workgroups applies: the standard 30 x 30 batch with ARCVecEnv's flags)
-  StepParams pf = e->base;
-  pf.flags = flags;
   const bool pf_kernel = !e->big && width_class(e->base) == arcle::FW_FULL && e->base.H == 30 && e->base.W == 30 && !e->d_acct &&
-                         launch_wpw(e) == WAVES_PER_WG && lean_twin(TW_PF, ingress, pf);
+                         launch_wpw(e) == WAVES_PER_WG && lean_twin(TW_PF, ingress, make_params(e, c));
   if (pf_kernel && n_steps > 1 && (n & 3) == 0 && sel) {
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, sel) == hipSuccess && attr.type == hipMemoryTypeHost) prefetch = true;
@@ -1538,9 +1608,7 @@ extern "C" int arcle_step_many(arcle_env* e, int ingress, int32_t n_steps, const
   if (prefetch && !e->d_stage) {
     // (the staging buffer is allocated by the first such call OUTSIDE a stream capture: allocating would invalidate a capture in
     // progress — a captured call without it falls back to every wave reading its own record across PCIe)
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
-      (void)hipGetLastError();
+    if (is_capturing(stream)) {
       prefetch = false;
     } else {
       DeviceGuard guard(e->device);
@@ -1553,19 +1621,18 @@ extern "C" int arcle_step_many(arcle_env* e, int ingress, int32_t n_steps, const
   // (device-resident payloads need nothing here: the launches of the standard batch order themselves, see launch_step)
   int rc = ARCLE_OK;
   for (int32_t t = 0; t < n_steps && rc == ARCLE_OK; t++) {
-    const void* src = (const char*)sel + (size_t)t * pb;
+    c.sel = (const char*)sel + (size_t)t * pb;
+    c.op = op ? op + (size_t)t * n : nullptr;
+    c.reward = reward ? reward + (size_t)t * n : nullptr;
+    c.term = term ? term + (size_t)t * n : nullptr;
     if (prefetch) {
-      if (t > 0) src = e->d_stage + (size_t)(t & 1) * n * 5;
-      e->pf_next = t + 1 < n_steps ? (const int32_t*)((const char*)sel + (size_t)(t + 1) * pb) : nullptr;
-      e->pf_stage = e->d_stage + (size_t)((t + 1) & 1) * n * 5;
-      e->pf_active = 1;
+      if (t > 0) c.sel = e->d_stage + (size_t)(t & 1) * n * 5;
+      c.next_sel = t + 1 < n_steps ? (const int32_t*)((const char*)sel + (size_t)(t + 1) * pb) : nullptr;
+      c.stage_out = e->d_stage + (size_t)((t + 1) & 1) * n * 5;
+      c.in_step_many = 1;
     }
-    rc = launch_step(e, ingress, src, op ? op + (size_t)t * n : nullptr, reward ? reward + (size_t)t * n : nullptr,
-                     term ? term + (size_t)t * n : nullptr, flags, stream);
+    rc = launch_step(e, c, stream);
   }
-  e->pf_next = nullptr;
-  e->pf_stage = nullptr;
-  e->pf_active = 0;
   return rc;
 }
 
@@ -1606,12 +1673,11 @@ extern "C" int arcle_pack_mask_bits(arcle_env* e, const int8_t* sel, uint8_t* bi
   return ARCLE_OK;
 }
 
-template <int ING>
-static int launch_rollout_ing(int fw, dim3 g, dim3 b, hipStream_t st, const StepParams& p) {
-  // (the rollout keeps planes in registers: lane predication does not matter, FW_FULL shares FW_FAST's code)
+template <int ING, int FW>
+static int launch_rollout_tbl(dim3 g, dim3 b, hipStream_t st, const StepParams& p) {
   // feat: the research flags (arcle_rollout_ex) — the FEAT 1 rows of the table and arcle_rollout_feat_kernel; the others never take them
   const bool feat = (p.flags & ARCLE_ROLLOUT_FEAT_FLAGS) != 0u;
-  if (fw != arcle::FW_GENERIC && p.H == 30 && p.W == 30 && each_lean([&](auto row) {
+  if (FW != arcle::FW_GENERIC && p.H == 30 && p.W == 30 && each_lean([&](auto row) {
         constexpr int R = decltype(row)::value, FL = LEAN[R].fl;
         if constexpr (lean_has(R, TW_ROLLOUT, ING)) {
           if constexpr (LEAN[R].feat) {
@@ -1627,99 +1693,33 @@ static int launch_rollout_ing(int fw, dim3 g, dim3 b, hipStream_t st, const Step
       }))
     return ARCLE_OK;
   if constexpr (DEV_BUILD) return ARCLE_ERR_CONFIG;
-  else if (feat && fw != arcle::FW_GENERIC) hipLaunchKernelGGL((arcle_rollout_feat_kernel<ING, arcle::FW_FAST>), g, b, 0, st, p);
-  else if (feat) hipLaunchKernelGGL((arcle_rollout_feat_kernel<ING, arcle::FW_GENERIC>), g, b, 0, st, p);
-  else if (fw != arcle::FW_GENERIC) hipLaunchKernelGGL((arcle_rollout_kernel<ING, arcle::FW_FAST>), g, b, 0, st, p);
-  else hipLaunchKernelGGL((arcle_rollout_kernel<ING, arcle::FW_GENERIC>), g, b, 0, st, p);
+  else if (feat) hipLaunchKernelGGL((arcle_rollout_feat_kernel<ING, FW>), g, b, 0, st, p);
+  else hipLaunchKernelGGL((arcle_rollout_kernel<ING, FW>), g, b, 0, st, p);
   return ARCLE_OK;
 }
 
-static int launch_rollout(arcle_env* e, int ingress, int32_t n_steps, const void* sel, const int32_t* op, int32_t* reward,
-                          uint8_t* term, uint32_t flags, void* stream) {
-  if (!e || !sel || !op || !reward || !term) return ARCLE_ERR_ARG;
-  if (n_steps <= 0) return fail(e, ARCLE_ERR_ARG, "n_steps must be positive");
-  if (e->base.n_ops <= 0) return fail(e, ARCLE_ERR_CONFIG, "no op table installed (arcle_set_op_table)");
-  if (flags & ~(ARCLE_STEP_AUTORESET | ARCLE_STEP_ELIDE_SELECTED | ARCLE_STEP_CONTINUE_RULE | ARCLE_STEP_RESET_ON_SUBMIT | ARCLE_STEP_PACK_OBS))
+// The rollouts.  installed: arcle_rollout_bbox / _point / _mask — the flags the plain rollout kernels take, packed rows into the buffer
+// arcle_set_packed_output installed (`out` names it); otherwise ABI 6, arcle_rollout_ex: the research env's step flags and every step's
+// outputs in `out` (include/arcle_hip.h).  Everything is checked before anything is enqueued: a refused call writes nothing.
+static int launch_rollout(arcle_env* e, int ingress, int32_t n_steps, const void* sel, const int32_t* op, int32_t* reward, uint8_t* term,
+                          const arcle_rollout_out* out, uint32_t flags, bool installed, void* stream) {
+  if (!takes(ROW_FORMS, ingress)) return fail(e, ARCLE_ERR_ARG, "arcle_rollout_ex: ingress ARCLE_INGRESS_BBOX, _POINT or _MASK");
+  if (int rc = need_steps(e, n_steps)) return rc;
+  if (int rc = need_op_table(e)) return rc;
+  if (installed && (flags & ~(ARCLE_STEP_AUTORESET | ARCLE_STEP_ELIDE_SELECTED | ARCLE_STEP_CONTINUE_RULE | ARCLE_STEP_RESET_ON_SUBMIT | ARCLE_STEP_PACK_OBS)))
     return fail(e, ARCLE_ERR_ARG, "flag not supported by the rollout kernels");
-  if ((flags & (ARCLE_STEP_CONTINUE_RULE | ARCLE_STEP_RESET_ON_SUBMIT)) && ingress != arcle::INGRESS_MASK)
-    return fail(e, ARCLE_ERR_CONFIG, "the rollout kernels take ARCLE_STEP_CONTINUE_RULE / _RESET_ON_SUBMIT with mask ingress only");
-  if ((flags & ARCLE_STEP_CONTINUE_RULE) && !e->bufs.plane[ARCLE_PL_SELECTED])  // (as launch_step: the rule compares with `selected`)
-    return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_CONTINUE_RULE needs mask ingress and the `selected` plane");
-  if ((flags & ARCLE_STEP_PACK_OBS) && !e->pack_out)
-    return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_PACK_OBS without arcle_set_packed_output (rollouts: uint8 [n_steps][n_envs][arcle_packed_obs_size()])");
-  if (e->big) {
-    // "semantically identical to n_steps calls of arcle_step_*": for the workgroup-per-env kernels that is what a rollout is (the state does
-    // not fit a wavefront's registers); with ARCLE_STEP_PACK_OBS every step's rows go to its own slice of the installed buffer
-    const size_t n = (size_t)e->cfg.n_envs, pb = payload_bytes(e, ingress);
-    int8_t* const pack0 = e->pack_out;
-    int rc = ARCLE_OK;
-    for (int32_t t = 0; t < n_steps && rc == ARCLE_OK; t++) {
-      if (pack0) e->pack_out = pack0 + (size_t)t * n * (size_t)arcle_big::packed_stride(e->base.P);
-      rc = launch_step(e, ingress, (const char*)sel + (size_t)t * pb, op + (size_t)t * n, reward + (size_t)t * n, term + (size_t)t * n, flags, stream);
-    }
-    e->pack_out = pack0;
-    return rc;
-  }
-  DeviceGuard guard(e->device);
-  if (e->d_dense_cache) HIP_TRY(e, hipMemsetAsync(e->d_dense_cache, 0, (size_t)e->cfg.n_envs * 8, (hipStream_t)stream));  // (rollouts move grids, keep no pairs)
-  StepParams p = e->base;
-  p.ingress = ingress;
-  p.sel = sel;
-  p.op = op;
-  p.reward = reward;
-  p.term = term;
-  p.flags = flags;
-  p.acct = nullptr;
-  p.rmask = nullptr;
-  p.n_steps = n_steps;
-  p.pack_out = e->pack_out;
-  const dim3 g = grid_for(p.n_envs), b(64 * WAVES_PER_WG);
-  hipStream_t st = (hipStream_t)stream;
-  const int fw = width_class(p);
-  int rc;
-  if (ingress == arcle::INGRESS_BBOX) rc = launch_rollout_ing<arcle::INGRESS_BBOX>(fw, g, b, st, p);
-  else if (ingress == arcle::INGRESS_POINT) rc = launch_rollout_ing<arcle::INGRESS_POINT>(fw, g, b, st, p);
-  else rc = launch_rollout_ing<arcle::INGRESS_MASK>(fw, g, b, st, p);
-  if (rc != ARCLE_OK) return fail(e, rc, "this build of libarcle_hip has no rollout kernel for the configuration");
-  HIP_TRY(e, hipGetLastError());
-  return ARCLE_OK;
-}
-
-extern "C" int arcle_rollout_bbox(arcle_env* e, int32_t n_steps, const int32_t* bbox, const int32_t* op, int32_t* reward,
-                                  uint8_t* term, uint32_t flags, void* stream) {
-  return launch_rollout(e, arcle::INGRESS_BBOX, n_steps, bbox, op, reward, term, flags, stream);
-}
-extern "C" int arcle_rollout_point(arcle_env* e, int32_t n_steps, const int32_t* xy, const int32_t* op, int32_t* reward,
-                                   uint8_t* term, uint32_t flags, void* stream) {
-  return launch_rollout(e, arcle::INGRESS_POINT, n_steps, xy, op, reward, term, flags, stream);
-}
-extern "C" int arcle_rollout_mask(arcle_env* e, int32_t n_steps, const int8_t* sel, const int32_t* op, int32_t* reward,
-                                  uint8_t* term, uint32_t flags, void* stream) {
-  return launch_rollout(e, arcle::INGRESS_MASK, n_steps, sel, op, reward, term, flags, stream);
-}
-
-// ABI 6: a rollout with the research env's step flags and every step's outputs (include/arcle_hip.h).  Everything is checked before
-// anything is enqueued: a refused call writes nothing.
-extern "C" int arcle_rollout_ex(arcle_env* e, int ingress, int32_t n_steps, const void* sel, const int32_t* op, int32_t* reward,
-                                uint8_t* term, const arcle_rollout_out* out, uint32_t flags, void* stream) {
-  if (!e || !sel || !op || !reward || !term) return ARCLE_ERR_ARG;
-  if (ingress != arcle::INGRESS_BBOX && ingress != arcle::INGRESS_POINT && ingress != arcle::INGRESS_MASK)
-    return fail(e, ARCLE_ERR_ARG, "arcle_rollout_ex: ingress ARCLE_INGRESS_BBOX, _POINT or _MASK");
-  if (n_steps <= 0) return fail(e, ARCLE_ERR_ARG, "n_steps must be positive");
-  if (e->base.n_ops <= 0) return fail(e, ARCLE_ERR_CONFIG, "no op table installed (arcle_set_op_table)");
   if (flags & ~0x3ffu) return fail(e, ARCLE_ERR_ARG, "unknown step flag");
   if (flags & ARCLE_STEP_ROWS_INCREMENTAL) return fail(e, ARCLE_ERR_ARG, "rollouts write every row in full: no ARCLE_STEP_ROWS_INCREMENTAL");
   const uint32_t outputs = ARCLE_STEP_TRUNCATE | ARCLE_STEP_DENSE | ARCLE_STEP_FLAT_OBS | ARCLE_STEP_PACK_OBS;
   if ((flags & outputs) && !out) return fail(e, ARCLE_ERR_ARG, "arcle_rollout_ex: output flags without an arcle_rollout_out");
   if ((flags & (ARCLE_STEP_CONTINUE_RULE | ARCLE_STEP_RESET_ON_SUBMIT)) && ingress != arcle::INGRESS_MASK)
     return fail(e, ARCLE_ERR_CONFIG, "the rollout kernels take ARCLE_STEP_CONTINUE_RULE / _RESET_ON_SUBMIT with mask ingress only");
-  if ((flags & ARCLE_STEP_CONTINUE_RULE) && !e->bufs.plane[ARCLE_PL_SELECTED])
-    return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_CONTINUE_RULE needs mask ingress and the `selected` plane");
+  if (int rc = need_rule_planes(e, ingress, flags)) return rc;
   if (flags & ARCLE_STEP_TRUNCATE) {
     if (!out->trunc) return fail(e, ARCLE_ERR_ARG, "ARCLE_STEP_TRUNCATE without arcle_rollout_out.trunc");
     if (e->base.step_limit <= 0) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_TRUNCATE without a positive step limit (arcle_set_truncation)");
   }
-  if ((flags & ARCLE_STEP_RESAMPLE) && e->base.n_problems <= 0) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_RESAMPLE without arcle_set_sampler");
+  if (int rc = need_sampler(e, flags)) return rc;
   if (flags & ARCLE_STEP_DENSE) {
     if (!out->dense) return fail(e, ARCLE_ERR_ARG, "ARCLE_STEP_DENSE without arcle_rollout_out.dense");
     if (!e->bufs.plane[ARCLE_PL_ANSWER]) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_DENSE needs the answer plane");
@@ -1731,80 +1731,87 @@ extern "C" int arcle_rollout_ex(arcle_env* e, int ingress, int32_t n_steps, cons
     if (!out->rows || (reinterpret_cast<uintptr_t>(out->rows) & 15) || out->rows_stride != ((len + 15) & ~15))
       return fail(e, ARCLE_ERR_ARG, "arcle_rollout_ex rows: 16-byte aligned int8 [n_steps][n_envs][arcle_flat_obs_size() rounded up to 16]");
   }
+  if ((flags & ARCLE_STEP_PACK_OBS) && installed && !out->packed)
+    return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_PACK_OBS without arcle_set_packed_output (rollouts: uint8 [n_steps][n_envs][arcle_packed_obs_size()])");
   if ((flags & ARCLE_STEP_PACK_OBS) && (!out->packed || (reinterpret_cast<uintptr_t>(out->packed) & 15)))
     return fail(e, ARCLE_ERR_ARG, "arcle_rollout_ex packed: 16-byte aligned uint8 [n_steps][n_envs][arcle_packed_obs_size()]");
-  const size_t n = (size_t)e->cfg.n_envs;
-  if (e->big) {
-    // as arcle_rollout_*: n_steps step launches of the workgroup-per-env kernels, each pointed at its own slices of the outputs
-    // (the handle's installed outputs are restored afterwards)
-    const size_t pb = payload_bytes(e, ingress), rs = (size_t)(out ? out->rows_stride : 0), ps = (size_t)arcle_big::packed_stride(e->base.P);
-    uint8_t* const trunc0 = e->base.trunc;
-    int32_t* const dense0 = e->base.dense;
-    int8_t *const flat0 = e->flat_out, *const pack0 = e->pack_out;
-    const int32_t stride0 = e->flat_stride;
-    const int filt0 = e->flat_filtered, tail0 = e->flat_tail, seq0 = e->flat_seq;
-    int rc = ARCLE_OK;
-    for (int32_t t = 0; t < n_steps && rc == ARCLE_OK; t++) {
-      if (flags & ARCLE_STEP_TRUNCATE) e->base.trunc = out->trunc + (size_t)t * n;
-      if (flags & ARCLE_STEP_DENSE) e->base.dense = out->dense + 2 * (size_t)t * n;
-      if (flags & ARCLE_STEP_FLAT_OBS) {
-        e->flat_out = out->rows + (size_t)t * n * rs;
-        e->flat_stride = out->rows_stride;
-        e->flat_filtered = filtered;
-        e->flat_tail = 0;
-        e->flat_seq = 0;
-      }
-      if (flags & ARCLE_STEP_PACK_OBS) e->pack_out = reinterpret_cast<int8_t*>(out->packed) + (size_t)t * n * ps;
-      rc = launch_step(e, ingress, (const char*)sel + (size_t)t * pb, op + (size_t)t * n, reward + (size_t)t * n, term + (size_t)t * n, flags, stream);
+  const size_t n = (size_t)e->cfg.n_envs, pb = payload_bytes(e, ingress);
+  // the request of step t: the action arrays and every output the flags ask for at slice t (a big-grid handle's step launches pass the
+  // installed truncation / dense destinations along where the flags do not, as its plain steps do)
+  const StepCall c0 = e->big ? from_handle(e, ingress, sel, op, reward, term, flags) : action_call(ingress, sel, op, reward, term, flags);
+  auto slice = [&](size_t t) {
+    StepCall c = c0;
+    c.sel = (const char*)sel + t * pb;
+    c.op = op + t * n;
+    c.reward = reward + t * n;
+    c.term = term + t * n;
+    if (flags & ARCLE_STEP_TRUNCATE) c.trunc = out->trunc + t * n;
+    if (flags & ARCLE_STEP_DENSE) c.dense = out->dense + 2 * t * n;
+    if (flags & ARCLE_STEP_FLAT_OBS) {
+      c.flat_out = out->rows + t * n * (size_t)out->rows_stride;
+      c.flat_stride = out->rows_stride;
+      c.flat_filtered = filtered;
+      c.flat_tail = 0;
+      c.flat_seq = 0;
     }
-    e->base.trunc = trunc0;
-    e->base.dense = dense0;
-    e->flat_out = flat0;
-    e->pack_out = pack0;
-    e->flat_stride = stride0;
-    e->flat_filtered = filt0;
-    e->flat_tail = tail0;
-    e->flat_seq = seq0;
+    if (flags & ARCLE_STEP_PACK_OBS) c.pack_out = reinterpret_cast<int8_t*>(out->packed) + t * n * (size_t)arcle_big::packed_stride(e->base.P);
+    return c;
+  };
+  if (e->big) {
+    // "semantically identical to n_steps calls of arcle_step_*": for the workgroup-per-env kernels that is what a rollout is (the state does
+    // not fit a wavefront's registers) — n_steps step launches, each with the request of its own slices of the outputs
+    int rc = ARCLE_OK;
+    for (int32_t t = 0; t < n_steps && rc == ARCLE_OK; t++) rc = launch_step(e, slice((size_t)t), stream);
     return rc;
   }
   DeviceGuard guard(e->device);
-  if (e->d_dense_cache) HIP_TRY(e, hipMemsetAsync(e->d_dense_cache, 0, (size_t)e->cfg.n_envs * 8, (hipStream_t)stream));  // (rollouts move grids, keep no pairs)
-  StepParams p = e->base;
-  p.ingress = ingress;
-  p.sel = sel;
-  p.op = op;
-  p.reward = reward;
-  p.term = term;
-  p.flags = flags;
-  p.acct = nullptr;
-  p.rmask = nullptr;
+  if (int rc = drop_dense_cache(e, stream)) return rc;  // (rollouts move grids, keep no pairs)
+  // One launch: the request's bases are those of step 0, the kernel moves them by slice.  Outputs the flags do not ask for are NULL, the
+  // dense-pair cache too, for arcle_rollout_bbox / _point / _mask as well (they used to pass the installed truncation / dense destinations
+  // and the cache along): without TRUNCATE / DENSE no rollout kernel reads or writes the two outputs, and the cache was only ever
+  // re-zeroed (dense_forget) right after the drop above — same memory afterwards, a few stores fewer.
+  StepParams p = make_params(e, slice(0));
   p.n_steps = n_steps;
   p.dense_cache = nullptr;
-  p.trunc = (flags & ARCLE_STEP_TRUNCATE) ? out->trunc : nullptr;
-  p.dense = (flags & ARCLE_STEP_DENSE) ? out->dense : nullptr;
-  p.flat_out = (flags & ARCLE_STEP_FLAT_OBS) ? out->rows : nullptr;
-  p.flat_stride = (flags & ARCLE_STEP_FLAT_OBS) ? out->rows_stride : 0;
-  p.flat_filter = filtered;
-  p.flat_tail = 0;
-  p.flat_seq = 0;
-  p.pack_out = (flags & ARCLE_STEP_PACK_OBS) ? reinterpret_cast<int8_t*>(out->packed) : nullptr;
   const dim3 g = grid_for(p.n_envs), b(64 * WAVES_PER_WG);
-  hipStream_t st = (hipStream_t)stream;
-  const int fw = width_class(p);
-  int rc;
-  if (ingress == arcle::INGRESS_BBOX) rc = launch_rollout_ing<arcle::INGRESS_BBOX>(fw, g, b, st, p);
-  else if (ingress == arcle::INGRESS_POINT) rc = launch_rollout_ing<arcle::INGRESS_POINT>(fw, g, b, st, p);
-  else rc = launch_rollout_ing<arcle::INGRESS_MASK>(fw, g, b, st, p);
+  const int rc = with_form<ROW_FORMS, false>(ingress, width_class(p), [&](auto ing, auto fw) {
+    return launch_rollout_tbl<decltype(ing)::value, decltype(fw)::value>(g, b, (hipStream_t)stream, p);
+  });
   if (rc != ARCLE_OK) return fail(e, rc, "this build of libarcle_hip has no rollout kernel for the configuration");
   HIP_TRY(e, hipGetLastError());
   return ARCLE_OK;
+}
+
+static int rollout_installed(arcle_env* e, int ingress, int32_t n_steps, const void* sel, const int32_t* op, int32_t* reward, uint8_t* term,
+                             uint32_t flags, void* stream) {
+  if (!e || !sel || !op || !reward || !term) return ARCLE_ERR_ARG;
+  arcle_rollout_out out = {};
+  out.packed = reinterpret_cast<uint8_t*>(from_handle(e, ingress, sel, op, reward, term, flags).pack_out);
+  return launch_rollout(e, ingress, n_steps, sel, op, reward, term, &out, flags, true, stream);
+}
+extern "C" int arcle_rollout_bbox(arcle_env* e, int32_t n_steps, const int32_t* bbox, const int32_t* op, int32_t* reward,
+                                  uint8_t* term, uint32_t flags, void* stream) {
+  return rollout_installed(e, arcle::INGRESS_BBOX, n_steps, bbox, op, reward, term, flags, stream);
+}
+extern "C" int arcle_rollout_point(arcle_env* e, int32_t n_steps, const int32_t* xy, const int32_t* op, int32_t* reward,
+                                   uint8_t* term, uint32_t flags, void* stream) {
+  return rollout_installed(e, arcle::INGRESS_POINT, n_steps, xy, op, reward, term, flags, stream);
+}
+extern "C" int arcle_rollout_mask(arcle_env* e, int32_t n_steps, const int8_t* sel, const int32_t* op, int32_t* reward,
+                                  uint8_t* term, uint32_t flags, void* stream) {
+  return rollout_installed(e, arcle::INGRESS_MASK, n_steps, sel, op, reward, term, flags, stream);
+}
+extern "C" int arcle_rollout_ex(arcle_env* e, int ingress, int32_t n_steps, const void* sel, const int32_t* op, int32_t* reward,
+                                uint8_t* term, const arcle_rollout_out* out, uint32_t flags, void* stream) {
+  if (!e || !sel || !op || !reward || !term) return ARCLE_ERR_ARG;
+  return launch_rollout(e, ingress, n_steps, sel, op, reward, term, out, flags, false, stream);
 }
 
 extern "C" int arcle_set_sampler(arcle_env* e, const int32_t* pair_off, const int32_t* pair_cnt, int32_t n_problems, uint64_t seed,
                                  int64_t env_base, int32_t* episode, int32_t* cur_task, uint32_t aug_flags) {
   if (!e || !pair_off || !pair_cnt || !episode) return ARCLE_ERR_ARG;
   if (n_problems <= 0) return fail(e, ARCLE_ERR_CONFIG, "the sampler needs at least one problem with a pair");
-  if (e->base.n_tasks <= 0) return fail(e, ARCLE_ERR_CONFIG, "no task table installed (arcle_set_task_table)");
+  if (int rc = need_task_table(e)) return rc;
   if (aug_flags & ~(ARCLE_AUG_PERMUTE | ARCLE_AUG_ROT90)) return fail(e, ARCLE_ERR_ARG, "unknown augmentation flag");
   e->base.pair_off = pair_off;
   e->base.pair_cnt = pair_cnt;
@@ -1820,42 +1827,14 @@ extern "C" int arcle_set_sampler(arcle_env* e, const int32_t* pair_off, const in
 extern "C" int arcle_reset_sampled(arcle_env* e, const uint8_t* mask, void* stream) {
   if (!e) return ARCLE_ERR_ARG;
   if (e->base.n_problems <= 0) return fail(e, ARCLE_ERR_CONFIG, "no sampler installed (arcle_set_sampler)");
-  DeviceGuard guard(e->device);
-  if (e->big) {
-    arcle_big::BigParams q = big_params(e);
-    q.rmask = mask;
-    return big_done(e, arcle_big::launch_reset(q, 2, stream), "arcle_reset_sampled");
-  }
-  StepParams p = e->base;
-  p.rmask = mask;
-  p.task_idx = nullptr;
-  hipLaunchKernelGGL(arcle_reset_table_kernel, grid_for(p.n_envs), dim3(64 * WAVES_PER_WG), 0, (hipStream_t)stream, p);
-  HIP_TRY(e, hipGetLastError());
-  return ARCLE_OK;
+  return launch_reset(e, 2, mask, nullptr, nullptr, nullptr, "arcle_reset_sampled", stream);
 }
 
 extern "C" int arcle_reset_from_table_aug(arcle_env* e, const int32_t* task_idx, const uint8_t* mask, const uint8_t* aug_k,
                                           const uint8_t* aug_perm, void* stream) {
   if (!e || !task_idx) return ARCLE_ERR_ARG;
-  if (e->base.n_tasks <= 0) return fail(e, ARCLE_ERR_CONFIG, "no task table installed (arcle_set_task_table)");
-  if (e->big) {
-    DeviceGuard guard(e->device);
-    arcle_big::BigParams q = big_params(e);
-    q.rmask = mask;
-    q.task_idx = task_idx;
-    q.aug_k = aug_k;
-    q.aug_perm = aug_perm;
-    return big_done(e, arcle_big::launch_reset(q, 1, stream), "arcle_reset_from_table_aug");
-  }
-  DeviceGuard guard(e->device);
-  StepParams p = e->base;
-  p.rmask = mask;
-  p.task_idx = task_idx;
-  p.aug_k = aug_k;
-  p.aug_perm = aug_perm;
-  hipLaunchKernelGGL(arcle_reset_table_kernel, grid_for(p.n_envs), dim3(64 * WAVES_PER_WG), 0, (hipStream_t)stream, p);
-  HIP_TRY(e, hipGetLastError());
-  return ARCLE_OK;
+  if (int rc = need_task_table(e)) return rc;
+  return launch_reset(e, 1, mask, task_idx, aug_k, aug_perm, "arcle_reset_from_table_aug", stream);
 }
 
 extern "C" int arcle_set_dense_output(arcle_env* e, int32_t* dense_out) {
@@ -1876,11 +1855,8 @@ extern "C" int arcle_set_dense_output(arcle_env* e, int32_t* dense_out) {
 
 extern "C" int arcle_invalidate(arcle_env* e, void* stream) {
   if (!e) return ARCLE_ERR_ARG;
-  if (e->d_dense_cache) {
-    DeviceGuard guard(e->device);
-    HIP_TRY(e, hipMemsetAsync(e->d_dense_cache, 0, (size_t)e->cfg.n_envs * 8, (hipStream_t)stream));
-  }
-  return ARCLE_OK;
+  DeviceGuard guard(e->device);
+  return drop_dense_cache(e, stream);
 }
 
 extern "C" int arcle_set_truncation(arcle_env* e, uint8_t* trunc_out, int32_t step_limit) {
@@ -1897,11 +1873,20 @@ extern "C" int arcle_flat_obs_size(const arcle_env* e, int filtered) {
   return arcle::flat_obs_len(e->base, filtered);  // (the same formula for any H x W)
 }
 
-static int launch_flatten(arcle_env* e, int8_t* out, int32_t out_stride, int filtered, hipStream_t st) {
+// rows a flatten launch or a fused step may write: the subset exists for this env kind, alignment, stride (with room for a tail where asked)
+static int check_flat_rows(arcle_env* e, const int8_t* out, int32_t out_stride, int filtered, int tail) {
   const int len = arcle_flat_obs_size(e, filtered);
+  if (tail && len >= 0 && out_stride < ((len + 15) & ~15) + 16)
+    return fail(e, ARCLE_ERR_ARG, "flat rows with a tail: stride >= arcle_flat_obs_size() rounded up to 16, plus 16");
   if (len < 0) return fail(e, ARCLE_ERR_CONFIG, "the FilterO2ARC subset needs the O2ARCv2Env state planes");
   if (out_stride < len || (out_stride & 15) || (reinterpret_cast<uintptr_t>(out) & 15))
     return fail(e, ARCLE_ERR_ARG, "flat observation rows: 16-byte aligned, stride a multiple of 16 >= arcle_flat_obs_size()");
+  return ARCLE_OK;
+}
+
+static int launch_flatten(arcle_env* e, int8_t* out, int32_t out_stride, int filtered, hipStream_t st) {
+  if (int rc = check_flat_rows(e, out, out_stride, filtered, 0)) return rc;
+  const int len = arcle_flat_obs_size(e, filtered);
   if (e->big) {
     arcle_big::BigParams q = big_params(e);
     q.flat_out = out;
@@ -1926,31 +1911,19 @@ extern "C" int arcle_flatten_obs(arcle_env* e, int8_t* out, int32_t out_stride, 
   return launch_flatten(e, out, out_stride, filtered, (hipStream_t)stream);
 }
 
-extern "C" int arcle_set_flat_output(arcle_env* e, int8_t* out, int32_t out_stride, int filtered) {
+extern "C" int arcle_set_flat_output_ex(arcle_env* e, int8_t* out, int32_t out_stride, int filtered, int tail) {
   if (!e) return ARCLE_ERR_ARG;
-  if (out) {
-    const int len = arcle_flat_obs_size(e, filtered);
-    if (len < 0) return fail(e, ARCLE_ERR_CONFIG, "the FilterO2ARC subset needs the O2ARCv2Env state planes");
-    if (out_stride < len || (out_stride & 15) || (reinterpret_cast<uintptr_t>(out) & 15))
-      return fail(e, ARCLE_ERR_ARG, "flat observation rows: 16-byte aligned, stride a multiple of 16 >= arcle_flat_obs_size()");
-  }
+  if (out)
+    if (int rc = check_flat_rows(e, out, out_stride, filtered, tail)) return rc;
   e->flat_out = out;
   e->flat_stride = out_stride;
   e->flat_filtered = filtered ? 1 : 0;
-  e->flat_tail = 0;
+  e->flat_tail = (out && tail) ? 1 : 0;
   return ARCLE_OK;
 }
 
-extern "C" int arcle_set_flat_output_ex(arcle_env* e, int8_t* out, int32_t out_stride, int filtered, int tail) {
-  if (!e) return ARCLE_ERR_ARG;
-  if (out && tail) {
-    const int len = arcle_flat_obs_size(e, filtered);
-    if (len >= 0 && out_stride < ((len + 15) & ~15) + 16)
-      return fail(e, ARCLE_ERR_ARG, "flat rows with a tail: stride >= arcle_flat_obs_size() rounded up to 16, plus 16");
-  }
-  const int rc = arcle_set_flat_output(e, out, out_stride, filtered);
-  if (rc == ARCLE_OK) e->flat_tail = (out && tail) ? 1 : 0;
-  return rc;
+extern "C" int arcle_set_flat_output(arcle_env* e, int8_t* out, int32_t out_stride, int filtered) {
+  return arcle_set_flat_output_ex(e, out, out_stride, filtered, 0);
 }
 
 extern "C" int arcle_set_flat_seq(arcle_env* e, int32_t seq) {
@@ -1993,45 +1966,41 @@ extern "C" int arcle_get_state_rows(arcle_env* e, int8_t* rows, int32_t stride, 
   return launch_flatten(e, rows, stride, 0, (hipStream_t)stream);
 }
 
-template <int ING>
-static void launch_transition_ing(int fw, dim3 g, dim3 b, hipStream_t st, const StepParams& p) {
-  // (planes live in registers: lane predication does not matter, FW_FULL shares FW_FAST's code — as in the rollout kernels)
-  if (fw != arcle::FW_GENERIC) hipLaunchKernelGGL((arcle_transition_rows_kernel<ING, arcle::FW_FAST>), g, b, 0, st, p);
-  else hipLaunchKernelGGL((arcle_transition_rows_kernel<ING, arcle::FW_GENERIC>), g, b, 0, st, p);
-}
-
 extern "C" int arcle_transition_rows(arcle_env* e, int32_t n_rows, const int8_t* rows_in, int32_t in_stride, int ingress,
                                      const void* sel, const int32_t* op, const int32_t* src_env, int8_t* rows_out,
                                      int32_t out_stride, int tail, int32_t* reward, uint8_t* term, uint32_t flags, void* stream) {
   if (!e || !sel || !op || !reward || !term || !rows_out) return ARCLE_ERR_ARG;
   if (n_rows <= 0) return fail(e, ARCLE_ERR_ARG, "n_rows must be positive");
-  if (!src_env && n_rows > e->cfg.n_envs) return fail(e, ARCLE_ERR_ARG, "more rows than envs: pass src_env (which env's answer every row uses)");
+  if (int rc = need_src_env(e, n_rows, src_env)) return rc;
   if ((uint64_t)n_rows * ARCLE_MAX_CELLS >= (1ull << 32)) return fail(e, ARCLE_ERR_ARG, "too many rows");
-  if (e->base.n_ops <= 0) return fail(e, ARCLE_ERR_CONFIG, "no op table installed (arcle_set_op_table)");
+  if (int rc = need_op_table(e)) return rc;
   if (flags & ~(ARCLE_STEP_RESET_ON_SUBMIT | ARCLE_STEP_DENSE | ARCLE_STEP_CONTINUE_RULE))
     return fail(e, ARCLE_ERR_ARG, "arcle_transition_rows takes ARCLE_STEP_RESET_ON_SUBMIT / _DENSE / _CONTINUE_RULE only");
-  if ((flags & ARCLE_STEP_DENSE) && !e->base.dense) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_DENSE without arcle_set_dense_output");
+  // the request: dense pairs where arcle_set_dense_output put them, the rows (and the tail's sequence number) as this call says; no accounting
+  StepCall c = from_handle(e, ingress, sel, op, reward, term, flags);
+  c.flat_out = rows_out;
+  c.flat_stride = out_stride;
+  c.flat_filtered = 0;
+  c.flat_tail = tail;
+  c.acct = nullptr;
+  if ((flags & ARCLE_STEP_DENSE) && !c.dense) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_DENSE without arcle_set_dense_output");
   if ((flags & ARCLE_STEP_DENSE) && n_rows > e->cfg.n_envs) return fail(e, ARCLE_ERR_ARG, "ARCLE_STEP_DENSE: the dense output has one pair per env, n_rows <= n_envs");
-  if ((flags & ARCLE_STEP_CONTINUE_RULE) && ingress != arcle::INGRESS_MASK) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_CONTINUE_RULE needs mask ingress");
+  if (int rc = need_rule_mask(e, ingress, flags)) return rc;
   if (int rc = check_rows(e, rows_in, in_stride, 0)) return rc;
   const int len = arcle::flat_obs_len(e->base, 0);
   if ((out_stride & 15) || (reinterpret_cast<uintptr_t>(rows_out) & 15) || out_stride < ((len + 15) & ~15) + (tail ? 16 : 0))
     return fail(e, ARCLE_ERR_ARG, "output rows: 16-byte aligned, stride a multiple of 16 >= the row length (+16 with a tail)");
+  if (!takes(ROW_FORMS, ingress)) return fail(e, ARCLE_ERR_ARG, "arcle_transition_rows takes mask, bbox or point selections");  // (before any allocation or launch)
   DeviceGuard guard(e->device);
   if (e->big) {
     // the state does not fit a wavefront, so the stateless transition is three launches over SCRATCH envs (one per row): rows -> scratch
     // planes / records (+ the answer of resident env src_env[r]), one step() of the scratch envs with the fused row writer, i.e.
     // row r of rows_out = FlattenObservation of the stepped state (+ tail).  The resident envs are not touched.  The scratch (8 planes +
     // record + counters per row) is allocated — or grown — here: not inside a stream capture.
-    if (ingress != arcle::INGRESS_MASK && ingress != arcle::INGRESS_BBOX && ingress != arcle::INGRESS_POINT)  // (before any allocation or launch)
-      return fail(e, ARCLE_ERR_ARG, "arcle_transition_rows takes mask, bbox or point selections");
     const size_t PS = (size_t)e->base.PS, per_row = ARCLE_N_PLANES * PS + ARCLE_REC_BYTES + 8;
     if (n_rows > e->big_scratch_rows) {
-      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-      if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
-        (void)hipGetLastError();
+      if (is_capturing(stream))
         return fail(e, ARCLE_ERR_CONFIG, "arcle_transition_rows of a big-grid handle allocates its scratch envs on first use: call it once outside the stream capture");
-      }
       if (e->big_scratch) {
         HIP_TRY(e, hipDeviceSynchronize());
         (void)hipFree(e->big_scratch);
@@ -2041,63 +2010,38 @@ extern "C" int arcle_transition_rows(arcle_env* e, int32_t n_rows, const int8_t*
       HIP_TRY(e, hipMalloc((void**)&e->big_scratch, per_row * (size_t)n_rows));
       e->big_scratch_rows = n_rows;
     }
-    arcle_big::BigParams q = big_params(e);
     const size_t R = (size_t)e->big_scratch_rows;
-    for (int i = 0; i < ARCLE_N_PLANES; i++) q.plane[i] = e->bufs.plane[i] ? e->big_scratch + (size_t)i * R * PS : nullptr;
-    q.rec = e->big_scratch + ARCLE_N_PLANES * R * PS;
-    q.cnt = reinterpret_cast<int32_t*>(e->big_scratch + ARCLE_N_PLANES * R * PS + R * ARCLE_REC_BYTES);
-    q.n_envs = n_rows;
-    q.n_resident = e->cfg.n_envs;
-    q.src_env = src_env;
-    q.res_answer = e->bufs.plane[ARCLE_PL_ANSWER];
-    q.res_rec = e->bufs.rec;
-    q.rows_in = rows_in;
-    q.rows_in_stride = in_stride;
-    if (int rc = big_done(e, arcle_big::launch_set_rows(q, stream), "arcle_transition_rows (rows in)")) return rc;
-    q.ingress = ingress;
-    q.sel = sel;
-    q.op = op;
-    q.reward = reward;
-    q.term = term;
-    q.flags = flags | ARCLE_STEP_FLAT_OBS;
-    q.dense = e->base.dense;
-    q.flat_out = rows_out;
-    q.flat_stride = out_stride;
-    q.flat_filter = 0;
-    q.flat_tail = tail ? 1 : 0;
-    q.flat_seq = tail ? e->flat_seq : 0;
-    return big_done(e, arcle_big::launch_step(q, stream), "arcle_transition_rows");
+    auto on_scratch = [&](arcle_big::BigParams q) {
+      for (int i = 0; i < ARCLE_N_PLANES; i++) q.plane[i] = e->bufs.plane[i] ? e->big_scratch + (size_t)i * R * PS : nullptr;
+      q.rec = e->big_scratch + ARCLE_N_PLANES * R * PS;
+      q.cnt = reinterpret_cast<int32_t*>(e->big_scratch + ARCLE_N_PLANES * R * PS + R * ARCLE_REC_BYTES);
+      q.n_envs = n_rows;
+      q.n_resident = e->cfg.n_envs;
+      q.src_env = src_env;
+      q.res_answer = e->bufs.plane[ARCLE_PL_ANSWER];
+      q.res_rec = e->bufs.rec;
+      q.rows_in = rows_in;
+      q.rows_in_stride = in_stride;
+      return q;
+    };
+    if (int rc = big_done(e, arcle_big::launch_set_rows(on_scratch(big_params(e)), stream), "arcle_transition_rows (rows in)")) return rc;
+    c.flags |= ARCLE_STEP_FLAT_OBS;
+    return big_done(e, arcle_big::launch_step(on_scratch(make_big_params(e, c)), stream), "arcle_transition_rows");
   }
-  StepParams p = e->base;
+  StepParams p = make_params(e, c);
+  fill_rows(p, c);  // (the row kernel writes its rows without being asked by a flag)
   p.n_resident = p.n_envs;
   p.n_envs = n_rows;
-  p.ingress = ingress;
-  p.sel = sel;
-  p.op = op;
-  p.reward = reward;
-  p.term = term;
-  p.flags = flags;
-  p.acct = nullptr;
-  p.rmask = nullptr;
   p.task_idx = src_env;
   p.rows_in = rows_in;
   p.rows_in_stride = in_stride;
-  p.flat_out = rows_out;
-  p.flat_stride = out_stride;
-  p.flat_filter = 0;
-  p.flat_tail = tail ? 1 : 0;
-  p.flat_seq = tail ? e->flat_seq : 0;
   // in place: a plane the op did not touch stays where it is (the writer's incremental mode); otherwise it is passed through
   if (rows_out == rows_in && out_stride == in_stride) p.flags |= ARCLE_STEP_ROWS_INCREMENTAL;
   const dim3 g = grid_for(n_rows), b(64 * WAVES_PER_WG);
-  hipStream_t st = (hipStream_t)stream;
-  const int fw = width_class(e->base);
-  switch (ingress) {
-    case arcle::INGRESS_BBOX: launch_transition_ing<arcle::INGRESS_BBOX>(fw, g, b, st, p); break;
-    case arcle::INGRESS_POINT: launch_transition_ing<arcle::INGRESS_POINT>(fw, g, b, st, p); break;
-    case arcle::INGRESS_MASK: launch_transition_ing<arcle::INGRESS_MASK>(fw, g, b, st, p); break;
-    default: return fail(e, ARCLE_ERR_ARG, "arcle_transition_rows takes mask, bbox or point selections");
-  }
+  with_form<ROW_FORMS, false>(ingress, width_class(e->base), [&](auto ing, auto fw) {
+    hipLaunchKernelGGL((arcle_transition_rows_kernel<decltype(ing)::value, decltype(fw)::value>), g, b, 0, (hipStream_t)stream, p);
+    return ARCLE_OK;
+  });
   HIP_TRY(e, hipGetLastError());
   return ARCLE_OK;
 }
@@ -2118,13 +2062,6 @@ extern "C" int arcle_hash_rows(arcle_env* e, int32_t n_rows, const int8_t* rows,
   hipLaunchKernelGGL(arcle_hash_rows_kernel, grid_for(n_rows), dim3(64 * WAVES_PER_WG), 0, (hipStream_t)stream, x);
   HIP_TRY(e, hipGetLastError());
   return ARCLE_OK;
-}
-
-template <int ING>
-static void launch_expand_ing(int fw, dim3 g, dim3 b, hipStream_t st, const arcle::ExpandParams& x) {
-  // (planes live in registers: FW_FULL shares FW_FAST's code, as in the row and rollout kernels)
-  if (fw != arcle::FW_GENERIC) hipLaunchKernelGGL((arcle_expand_kernel<ING, arcle::FW_FAST>), g, b, 0, st, x);
-  else hipLaunchKernelGGL((arcle_expand_kernel<ING, arcle::FW_GENERIC>), g, b, 0, st, x);
 }
 
 // Actions per wavefront.  A wave pays one pass over its parent's planes (7 loads + their hash terms) before its first action, so
@@ -2152,40 +2089,30 @@ extern "C" int arcle_expand_rows(arcle_env* e, int32_t n_rows, const int8_t* row
   if (n_rows <= 0 || n_actions <= 0) return fail(e, ARCLE_ERR_ARG, "n_rows and n_actions must be positive");
   if (action_row_stride != 0 && action_row_stride != n_actions)
     return fail(e, ARCLE_ERR_ARG, "action_row_stride: 0 (one action set for every row) or n_actions (a set per row)");
-  if (ingress != arcle::INGRESS_BBOX && ingress != arcle::INGRESS_POINT) return fail(e, ARCLE_ERR_ARG, "arcle_expand_rows takes bbox or point selections");
+  if (!takes(I_BBOX | I_POINT, ingress)) return fail(e, ARCLE_ERR_ARG, "arcle_expand_rows takes bbox or point selections");
   if (e->big) return fail(e, ARCLE_ERR_CONFIG, "arcle_expand_rows: handles of at most 1024 cells per plane (ARCLE_MAX_CELLS); larger grids expand through arcle_transition_rows");
-  if (!src_env && n_rows > e->cfg.n_envs) return fail(e, ARCLE_ERR_ARG, "more rows than envs: pass src_env (which env's answer every row uses)");
+  if (int rc = need_src_env(e, n_rows, src_env)) return rc;
   if ((int64_t)n_rows * n_actions >= (1ll << 28)) return fail(e, ARCLE_ERR_ARG, "too many children (n_rows * n_actions < 2^28)");
-  if (e->base.n_ops <= 0) return fail(e, ARCLE_ERR_CONFIG, "no op table installed (arcle_set_op_table)");
+  if (int rc = need_op_table(e)) return rc;
   if (dense) flags |= ARCLE_STEP_DENSE;
   if (flags & ~(ARCLE_STEP_RESET_ON_SUBMIT | ARCLE_STEP_DENSE | ARCLE_STEP_CONTINUE_RULE))
     return fail(e, ARCLE_ERR_ARG, "arcle_expand_rows takes ARCLE_STEP_RESET_ON_SUBMIT / _DENSE only");
-  if (flags & ARCLE_STEP_CONTINUE_RULE) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_CONTINUE_RULE needs mask ingress");
+  if (int rc = need_rule_mask(e, ingress, flags)) return rc;
   if ((flags & ARCLE_STEP_DENSE) && !dense) return fail(e, ARCLE_ERR_ARG, "ARCLE_STEP_DENSE without a dense output array");
   if ((flags & ARCLE_STEP_DENSE) && !e->bufs.plane[ARCLE_PL_ANSWER]) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_DENSE needs the answer plane");
   if (int rc = check_rows(e, rows, stride, 0)) return rc;
   DeviceGuard guard(e->device);
   arcle::ExpandParams x = {};
+  StepCall c = action_call(ingress, sel, op, reward, term, flags);  // (no output but the verdicts: rows, packed rows, truncation stay NULL)
+  c.dense = dense;
   StepParams& p = x.p;
-  p = e->base;
+  p = make_params(e, c);
   p.n_resident = p.n_envs;
   p.n_envs = n_rows;
-  p.ingress = ingress;
-  p.sel = sel;
-  p.op = op;
-  p.reward = reward;
-  p.term = term;
-  p.flags = flags;
-  p.acct = nullptr;
-  p.rmask = nullptr;
   p.task_idx = src_env;
   p.rows_in = rows;
   p.rows_in_stride = stride;
-  p.dense = dense;
   p.dense_cache = nullptr;
-  p.flat_out = nullptr;
-  p.pack_out = nullptr;
-  p.trunc = nullptr;
   p.status = e->d_status + 2;  // expansion is speculation: the handle's sticky word stays as it is
   x.n_actions = n_actions;
   x.action_row_stride = action_row_stride;
@@ -2195,10 +2122,10 @@ extern "C" int arcle_expand_rows(arcle_env* e, int32_t n_rows, const int8_t* row
   x.hash = hash;
   x.parent_hash = parent_hash;
   const dim3 g = grid_for(n_rows * x.n_chunks), b(64 * WAVES_PER_WG);
-  hipStream_t st = (hipStream_t)stream;
-  const int fw = width_class(e->base);
-  if (ingress == arcle::INGRESS_BBOX) launch_expand_ing<arcle::INGRESS_BBOX>(fw, g, b, st, x);
-  else launch_expand_ing<arcle::INGRESS_POINT>(fw, g, b, st, x);
+  with_form<I_BBOX | I_POINT, false>(ingress, width_class(e->base), [&](auto ing, auto fw) {
+    hipLaunchKernelGGL((arcle_expand_kernel<decltype(ing)::value, decltype(fw)::value>), g, b, 0, (hipStream_t)stream, x);
+    return ARCLE_OK;
+  });
   HIP_TRY(e, hipGetLastError());
   return ARCLE_OK;
 }
@@ -2228,7 +2155,7 @@ extern "C" int arcle_packed_obs_size(const arcle_env* e) {
 
 extern "C" int arcle_pack_obs(arcle_env* e, const int32_t* reward, const uint8_t* term, uint8_t* out, void* stream) {
   if (!e || !reward || !term || !out) return ARCLE_ERR_ARG;
-  if (reinterpret_cast<uintptr_t>(out) & 15) return fail(e, ARCLE_ERR_ARG, "packed observation rows must be 16-byte aligned");
+  if (int rc = check_packed(e, out)) return rc;
   DeviceGuard guard(e->device);
   if (e->big) {
     arcle_big::BigParams q = big_params(e);
@@ -2249,7 +2176,7 @@ extern "C" int arcle_pack_obs(arcle_env* e, const int32_t* reward, const uint8_t
 
 extern "C" int arcle_set_packed_output(arcle_env* e, uint8_t* out) {
   if (!e) return ARCLE_ERR_ARG;
-  if (reinterpret_cast<uintptr_t>(out) & 15) return fail(e, ARCLE_ERR_ARG, "packed observation rows must be 16-byte aligned");
+  if (int rc = check_packed(e, out)) return rc;
   e->pack_out = reinterpret_cast<int8_t*>(out);
   return ARCLE_OK;
 }

@@ -219,7 +219,7 @@ void lane_main(int lane) {
     arcle::wave_reset_table(*g_p, &g_lds.wave[0], g_lds.lut, g_env, lane);
   else if (g_kind == 3) {
     const int f = fw ? 1 : 0;  // (the library launches FW_FAST rollouts for FW_FULL too)
-    // as launch_rollout_ing (arcle_hip.hip): at 30 x 30, bbox / point rollouts with a lean flag set (AUTORESET | ELIDE_SELECTED, the same
+    // as launch_rollout_tbl (arcle_hip.hip): at 30 x 30, bbox / point rollouts with a lean flag set (AUTORESET | ELIDE_SELECTED, the same
     // plus PACK_OBS) run the twin whose flag set is a compile-time constant; every other rollout runs FL = -1
     constexpr int hot = ARCLE_STEP_AUTORESET | ARCLE_STEP_ELIDE_SELECTED;
     const int lean = (f && g_p->H == 30 && g_p->W == 30 && (g_p->ingress == 1 || g_p->ingress == 2))

@@ -47,6 +47,34 @@ def test_rollout_ex_big_grid_loops_step_launches():
     assert np.asarray(roll.episode).max() >= 3
 
 
+def test_step_after_big_grid_rollout_ex_writes_the_installed_outputs():
+    """A rollout's step launches carry their own destinations and leave the handle's alone: arcle_rollout_ex on a 40 x 40 handle with all
+    four outputs writes nothing into the buffers the setters installed, and the plain step after it (FLAT_OBS | PACK_OBS | TRUNCATE |
+    DENSE) fills them — rows, tail and sequence number included — exactly as on a twin that only ever stepped."""
+    N, SEQ = 24, 7
+    roll, twin, ops = RR.make_pair(RR.HipResearchBackend, RR.HipResearchBackend, 40, 40, N, 8, 0, step_limit=3, aug=0)
+    roll.set_flat_output(filtered=False, tail=True)
+    roll.set_packed_output()
+    assert roll.b.L.arcle_set_flat_seq(roll.b._h, SEQ) == 0
+    rng = np.random.default_rng(12)
+    pay, op = RR._actions(rng, ops, "bbox", N, 40, 40, 7)
+    errs = RR.compare(roll, twin, "bbox", pay[:6], op[:6], RR.RESAMPLE | RR.TRUNCATE | RR.DENSE | RR.FLAT_OBS | RR.PACK_OBS, "full", tag="40x40")
+    assert not errs, "\n".join(errs[:10])
+    torch.cuda.synchronize()
+    assert bool((roll.b._flat_buf == 0x55).all()) and bool((roll.b.packed == 0x55).all()), "the rollout wrote into the installed buffers"
+    twin.set_flat_output(filtered=False, tail=True)
+    twin.set_packed_output()
+    assert twin.b.L.arcle_set_flat_seq(twin.b._h, SEQ) == 0
+    flags = RR.FLAT_OBS | RR.PACK_OBS | RR.TRUNCATE | RR.DENSE
+    got, want = roll.step("bbox", pay[6], op[6], flags), twin.step("bbox", pay[6], op[6], flags)
+    for k, a, b in (("reward", got[0], want[0]), ("terminated", got[1], want[1]), ("trunc", roll.trunc, twin.trunc), ("dense", roll.dense, twin.dense),
+                    ("rows", roll.fused_flat(), twin.fused_flat()), ("tail", roll.fused_tail(), twin.fused_tail()),
+                    ("packed", roll.fused_packed(), twin.fused_packed())):
+        assert np.array_equal(np.asarray(a), np.asarray(b)), f"{k} of the step after the rollout differs from the twin's"
+    assert not (roll.fused_flat() == 0x55).all(1).any() and not (roll.fused_packed() == 0x55).all(1).any()
+    assert (((roll.fused_tail()[:, 3] >> 24) & 0xFF) == SEQ).all(), "the tail's sequence number"
+
+
 def test_mask_rollout_continue_rule_reset_on_submit_dense():
     errs = RR.mask_rules_compare(RR.HipResearchBackend, RR.HipResearchBackend, 30, 30, N=65, T=16, seed=9)
     assert not errs, "\n".join(errs[:10])

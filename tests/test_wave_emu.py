@@ -85,7 +85,7 @@ def test_emulated_mask_rollout_vs_oracle(H, W):
 @pytest.mark.parametrize("ingress", ["bbox", "point"])
 def test_emulated_lean_rollout_twins(ingress):
     """At 30 x 30 with AUTORESET | ELIDE_SELECTED (+ PACK_OBS) the emulator runs the rollout twin whose flag set is a compile-time
-    constant, as launch_rollout_ing does; out-of-range tuples and ops compare ARCLE_ST_BAD_SELECTION / _BAD_OP too."""
+    constant, as launch_rollout_tbl does; out-of-range tuples and ops compare ARCLE_ST_BAD_SELECTION / _BAD_OP too."""
     for flags in (3, 3 | B.STEP_PACK_OBS):
         errs = B.rollout_compare(B.EmuBackend, "o2arc", O.o2arc_ops(), 30, 30, N=6, T=40, seed=flags, ingress=ingress, flags=flags & 3,
                                  op_weights=OBJ_HEAVY, bad_ops=True, bad_tuples=True, packed=bool(flags & B.STEP_PACK_OBS))
