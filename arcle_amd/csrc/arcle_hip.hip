@@ -5,6 +5,7 @@
 //                              themselves inside groups of 32 envs (the GROUPED block)
 //   arcle_transition_rows_kernel  the stateless transition(state, action) on flattened state rows
 //   arcle_expand_kernel        K candidate actions per state row, verdicts and child hashes only (arcle_search.h); arcle_hash_rows_kernel
+//   arcle_components_kernel    the connected components of every state row's grid as ready-made actions (arcle_components.h)
 //   arcle_rollout_kernel       n_steps step()s per launch with the env state resident in registers
 //   arcle_reset[_table]_kernel init_state for (masked) envs, optionally from the device task table / device-drawn tasks
 //   arcle_flatten_kernel       flattened observation rows (also an epilogue of the step kernel: ARCLE_STEP_FLAT_OBS)
@@ -205,6 +206,7 @@ __device__ __forceinline__ void sink_v(uint32_t v) { asm volatile("" ::"v"(v)); 
 
 #include "arcle_wave.h"
 #include "arcle_search.h"      // state hash + K-actions-per-row expansion (arcle_hash_rows / arcle_expand_rows)
+#include "arcle_components.h"  // connected components of a row's grid as candidate actions (arcle_components_rows)
 #include "arcle_big_params.h"  // grids beyond ARCLE_MAX_CELLS: one workgroup per env (arcle_big.hip)
 
 using arcle::StepParams;
@@ -554,6 +556,15 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) __attribute__((amdgpu_waves_per_
   const uint32_t m = v / (uint32_t)x.n_chunks, j = v - m * (uint32_t)x.n_chunks;
   const int k0 = (int)j * x.chunk, k1 = k0 + x.chunk < x.n_actions ? k0 + x.chunk : x.n_actions;
   arcle::wave_expand_row<ING, FW>(x, &lds.wave[threadIdx.x >> 6], lds.lut, (int)m, k0, k1, (int)(threadIdx.x & 63));
+}
+
+// one wavefront per row, 4-wave workgroups; no LDS (the kernel neither stages a plane nor expands a mask: no table, no tile)
+static constexpr int COMP_WAVES_PER_WG = 4;
+template <int FW>
+__global__ __launch_bounds__(64 * COMP_WAVES_PER_WG) void arcle_components_kernel(const arcle::CompParams x) {
+  const int row = wave_of_launch(COMP_WAVES_PER_WG);
+  if (row >= x.p.n_envs) return;
+  arcle::wave_components_row<FW>(x, nullptr, nullptr, row, (int)(threadIdx.x & 63));
 }
 
 __global__ __launch_bounds__(64 * WAVES_PER_WG) void arcle_reset_kernel(const StepParams p) {
@@ -2126,6 +2137,37 @@ extern "C" int arcle_expand_rows(arcle_env* e, int32_t n_rows, const int8_t* row
     hipLaunchKernelGGL((arcle_expand_kernel<decltype(ing)::value, decltype(fw)::value>), g, b, 0, (hipStream_t)stream, x);
     return ARCLE_OK;
   });
+  HIP_TRY(e, hipGetLastError());
+  return ARCLE_OK;
+}
+
+// the connected components of every row's grid (arcle_components.h): reads the rows (or, rows == NULL, the resident grid planes and
+// records) and writes the caller's arrays — nothing of the handle is read beyond its geometry and nothing of it is written
+extern "C" int arcle_components_rows(arcle_env* e, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, int32_t skip_color,
+                                     int32_t* count, int32_t* comp, uint8_t* bits, void* stream) {
+  if (!e || !count || !comp) return ARCLE_ERR_ARG;
+  if (n_rows <= 0) return fail(e, ARCLE_ERR_ARG, "n_rows must be positive");
+  if (e->big) return fail(e, ARCLE_ERR_CONFIG, "arcle_components_rows: handles of at most 1024 cells per plane (ARCLE_MAX_CELLS)");
+  if (max_comp < 1 || max_comp > ARCLE_MAX_CELLS) return fail(e, ARCLE_ERR_ARG, "arcle_components_rows: max_comp in [1, ARCLE_MAX_CELLS]");
+  if (rows) {
+    if (int rc = check_rows(e, rows, stride, 0)) return rc;
+  } else if (n_rows > e->cfg.n_envs) {
+    return fail(e, ARCLE_ERR_ARG, "arcle_components_rows: rows == NULL labels the resident envs (n_rows <= n_envs)");
+  }
+  DeviceGuard guard(e->device);
+  arcle::CompParams x = {};
+  x.p = e->base;
+  x.p.n_envs = n_rows;
+  x.p.rows_in = rows;
+  x.p.rows_in_stride = rows ? stride : 0;
+  x.max_comp = max_comp;
+  x.skip_color = skip_color < 0 ? -1 : skip_color;
+  x.count = count;
+  x.comp = comp;
+  x.bits = bits;
+  const dim3 g = grid_for(n_rows, COMP_WAVES_PER_WG), b(64 * COMP_WAVES_PER_WG);
+  if (width_class(e->base) != arcle::FW_GENERIC) hipLaunchKernelGGL(arcle_components_kernel<arcle::FW_FAST>, g, b, 0, (hipStream_t)stream, x);
+  else hipLaunchKernelGGL(arcle_components_kernel<arcle::FW_GENERIC>, g, b, 0, (hipStream_t)stream, x);
   HIP_TRY(e, hipGetLastError());
   return ARCLE_OK;
 }

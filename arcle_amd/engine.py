@@ -629,6 +629,32 @@ class EnvBatch:
                                              _ptr(out.dense), _ptr(out.parent_hash), int(flags), self._stream()), "arcle_expand_rows")
         return out
 
+    def components_rows(self, rows=None, max_components=32, skip_color=-1, bits=False, out=None):
+        """The connected components (color.py:8-30: 4-connected, same colour, inside grid_dim) of the grid of every state row, each as
+        a ready-made action (arcle_components_rows): rows int8 [M, >= L] (any stride / alignment; read only), or None = the resident
+        envs.  Returns (count int32 [M, 2] = (written, left), comp int32 [M, C, 8] = x0, y0, x1, y1, sx, sy, colour, cells,
+        bits uint8 [M, C, 128] | None), C = max_components: components in ascending row-major order of their first cell (sx, sy),
+        the seed; the box inclusive, rows x / columns y as BBoxWrapper; cells of skip_color (-1: none) belong to no component; left =
+        the cells no written component holds; comp[m, k >= written] is not written.  bits: the cells in the layout of step_bits.
+        out: the tuple of a previous call with the same shapes to write into (captured graphs).  Nothing of the batch is touched."""
+        C = int(max_components)
+        if rows is None:
+            M, ptr, stride = self.N, None, 0
+        else:
+            assert rows.dtype == torch.int8 and rows.dim() == 2 and rows.stride(1) == 1
+            M, ptr, stride = int(rows.shape[0]), _ptr(rows), rows.stride(0)
+        if out is None:
+            dev = self.device
+            out = (torch.zeros((M, 2), dtype=torch.int32, device=dev), torch.zeros((M, C, 8), dtype=torch.int32, device=dev),
+                   torch.zeros((M, C, _lib.BITS_STRIDE), dtype=torch.uint8, device=dev) if bits else None)
+        count, comp, mbits = out
+        assert count.dtype == torch.int32 and tuple(count.shape) == (M, 2) and count.is_contiguous()
+        assert comp.dtype == torch.int32 and tuple(comp.shape) == (M, C, 8) and comp.is_contiguous()
+        assert (mbits is not None) == bool(bits) and (mbits is None or (mbits.dtype == torch.uint8 and tuple(mbits.shape) == (M, C, _lib.BITS_STRIDE) and mbits.is_contiguous()))
+        self._check(self.L.arcle_components_rows(self._h, M, ptr, stride, C, int(skip_color), _ptr(count), _ptr(comp), _ptr(mbits), self._stream()),
+                    "arcle_components_rows")
+        return out
+
     def get_plane(self, name, out=None):
         """One key of the state dict as a dense [N, H, W] int8 array (device tensor, or a pinned host tensor passed as `out`):
         arcle_get_plane, a strided copy on the current stream."""

@@ -13,6 +13,8 @@ at reset / auto-reset (keyed by the GLOBAL env id, so a sharded batch walks the 
 research env's epilogues (agents/env.py: dense reward, colour-permutation + rot90 augmentation; agents/train.py:67
 TimeLimit truncation).
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -20,6 +22,9 @@ from .. import actions, sampling
 from ..engine import (AUG_PERMUTE, AUG_ROT90, EnvBatch, capture_guard, STEP_AUTORESET, STEP_DENSE, STEP_FLAT_OBS, STEP_PACK_OBS, STEP_RESAMPLE,
                       STEP_RESET_ON_SUBMIT, STEP_ROWS_INCREMENTAL, STEP_TRUNCATE, ST_AUG_DOMAIN, ST_BAD_OP, ST_BAD_SELECTION, ST_BAD_TASK, ST_ROTATE_DOMAIN,
                       check_grid_size)
+
+# what ARCVecEnv.components returns: views of one int32 [M, C, 8] buffer (+ the count pair, + the optional bit masks)
+Components = collections.namedtuple("Components", "count left box seed color cells bits")
 
 
 def _table_of(env_cls, **ctor_kw):
@@ -592,6 +597,18 @@ class ARCVecEnv:
             src_env = src_env.to(device=self.device, dtype=torch.int32).contiguous()
         fl = STEP_RESET_ON_SUBMIT if self.flags & STEP_RESET_ON_SUBMIT else 0
         return self.batch.expand_rows(rows, form, pay, op, src_env, dense=True, flags=fl)
+
+    def components(self, rows=None, max_components=32, skip_color=-1, bits=False):
+        """The objects of every state's grid as ready-made actions — what a search proposes its candidates from (`arcle_amd.search`:
+        object_actions, propose_objects).  rows int8 [M, L] (as `state_rows` / `transition` return them) or None = this env's own
+        states.  Returns a Components of device tensors, views of one [M, C, 8] buffer (C = max_components): count [M] components
+        written and left [M] cells in none of them (0: the list is complete); box [M, C, 4] = (x0, y0, x1, y1) inclusive — a
+        BBoxWrapper action —, seed [M, C, 2] = the component's first cell in row-major order — a PointWrapper action and a FloodFill
+        seed —, color [M, C], cells [M, C]; bits [M, C, 128] (the cells in `step_bits`' layout) or None.  Components: 4-connected
+        cells of one colour inside grid_dim (the reference's dfs, color.py:8-30), in row-major order of their seeds; cells of
+        skip_color (-1: none; 0: ARC's background) belong to none.  Entries k >= count[m] are zero.  This env's state is not touched."""
+        count, comp, mbits = self.batch.components_rows(rows, max_components, skip_color, bits)
+        return Components(count[:, 0], count[:, 1], comp[:, :, 0:4], comp[:, :, 4:6], comp[:, :, 6], comp[:, :, 7], mbits)
 
     def autotune(self, payload, operation=None, form="bbox"):
         """Times every launch plan the library has for this env's steps (self-ordering or not, the cache policies of the speculative grid

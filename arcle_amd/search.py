@@ -1,5 +1,6 @@
-"""Search over ARCLE action sequences on top of `ARCVecEnv.expand`: the NumPy mirror of the device's state hash, and a plain beam
-search.
+"""Search over ARCLE action sequences on top of `ARCVecEnv.expand`: the NumPy mirror of the device's state hash, a plain beam
+search, and the objects of a grid as candidate actions (`components_numpy`: the host mirror of arcle_components_rows;
+`object_actions` / `propose_objects`: its descriptors as a per-state action set for `beam_search(propose=...)`).
 
 The hash is defined in include/arcle_hip.h (next to arcle_hash_rows) and computed on the device by arcle_amd/csrc/arcle_search.h;
 `hash_rows_numpy` restates it on the host — the same arrangement as arcle_amd/sampling.py for the device RNG — and is what the tests
@@ -93,7 +94,7 @@ def hash_rows_numpy(rows, kind, H, W):
 BeamResult = collections.namedtuple("BeamResult", "sequence counts root")
 
 
-def beam_search(venv, rows, actions, width, depth, src_env=None):
+def beam_search(venv, rows, actions, width, depth, src_env=None, propose=None):
     """Beam search over sequences drawn from ONE candidate action set, scored by the dense pair (correct cells / total cells).
 
     venv: anything with `expand(rows, action, src_env)`, `transition(rows, action, src_env)` and `hash_rows(rows)` as ARCVecEnv has
@@ -103,23 +104,37 @@ def beam_search(venv, rows, actions, width, depth, src_env=None):
     twice in this one: the lowest child index stays); if a child's grid IS the answer (correct == total: exactly when a Submit
     would pay — with unequal dims the total exceeds the common rectangle — so the candidate set needs no Submit) return the action
     indices that lead to the lowest such child; else keep the `width` best by correct / total, ties to the lower child index, and
-    materialise only those with `transition`.  Every tensor lives on rows.device."""
+    materialise only those with `transition`.  Every tensor lives on rows.device.
+
+    propose: a callable `propose(venv, frontier_rows) -> {"bbox": int32 [M, K, 4], "operation": int32 [M, K]}` called at every
+    depth for a candidate set PER STATE (`propose_objects`: the connected components of each state's grid); `actions` may then be
+    None, and BeamResult.sequence is the list of the 5-tuples (x1, y1, x2, y2, op) themselves — BBoxWrapper actions; an index into
+    a per-state set names nothing.  Slots with operation -1 are padding: their children carry a status bit and are dropped."""
     dev = rows.device
-    form = "bbox" if "bbox" in actions else "point"
-    pay = actions[form].to(device=dev, dtype=torch.int32).contiguous()
-    op = actions["operation"].to(device=dev, dtype=torch.int32).contiguous()
-    assert pay.dim() == 2 and op.dim() == 1, "beam_search takes one candidate set for every state"
-    K = int(op.shape[0])
+    if propose is None:
+        form = "bbox" if "bbox" in actions else "point"
+        pay = actions[form].to(device=dev, dtype=torch.int32).contiguous()
+        op = actions["operation"].to(device=dev, dtype=torch.int32).contiguous()
+        assert pay.dim() == 2 and op.dim() == 1, "beam_search takes one candidate set for every state"
+        K = int(op.shape[0])
+    else:
+        form = "bbox"
     M0 = int(rows.shape[0])
     src = (torch.arange(M0, device=dev) if src_env is None else src_env.to(dev)).to(torch.int32)
     root = torch.arange(M0, device=dev)
-    path = torch.empty((M0, 0), dtype=torch.int64, device=dev)
+    path = torch.empty((M0, 0), dtype=torch.int64, device=dev) if propose is None else torch.empty((M0, 0, 5), dtype=torch.int32, device=dev)
     seen = venv.hash_rows(rows)[:, 0].clone()
     frontier, counts = rows, []
     for _ in range(depth):
         M = int(frontier.shape[0])
         if M == 0:
             break
+        if propose is not None:
+            cand = propose(venv, frontier)
+            pay = cand["bbox"].to(device=dev, dtype=torch.int32).contiguous()
+            op = cand["operation"].to(device=dev, dtype=torch.int32).contiguous()
+            assert pay.dim() == 3 and op.dim() == 2 and pay.shape[0] == M, "propose returns a candidate set per frontier row"
+            K = int(op.shape[1])
         ex = venv.expand(frontier, {form: pay, "operation": op}, src)
         h = ex.hash[:, :, 0]
         ok = (ex.status == 0) & (h != ex.parent_hash[:, :1])
@@ -137,24 +152,99 @@ def beam_search(venv, rows, actions, width, depth, src_env=None):
         d2 = ex.dense.reshape(-1, 2)[idx].to(torch.int64)
         c, t = d2[:, 0], d2[:, 1]
         parent, k = idx // K, idx % K
+        if propose is None:
+            step_pay, step_op, step = pay.index_select(0, k), op.index_select(0, k), k.reshape(-1, 1)
+        else:  # the survivors' actions, gathered from their parents' sets
+            step_pay, step_op = pay.reshape(-1, 4).index_select(0, idx), op.reshape(-1).index_select(0, idx)
+            step = torch.cat([step_pay, step_op.reshape(-1, 1)], 1).reshape(-1, 1, 5)
         goal = (c == t) & (t > 0)
         if bool(goal.any()):
             g = int(torch.nonzero(goal)[0])
             counts.append((M * K, int(idx.numel()), 0))
-            seq = path[parent[g]].tolist() + [int(k[g])]
+            if propose is None:
+                seq = path[parent[g]].tolist() + [int(k[g])]
+            else:
+                seq = [tuple(a) for a in torch.cat([path[parent[g]], step[g]], 0).tolist()]
             return BeamResult(seq, counts, int(root[parent[g]]))
         # correct / total as an integer key: floor(c * 2^32 / t).  Two different fractions with totals below 2^16 differ by at least
         # 1 / (t1 * t2) > 2^-32, so their keys differ in the same direction; equal fractions give equal keys
         key = (c << 32) // torch.clamp(t, min=1)
         best = torch.argsort(key, descending=True, stable=True)[:width]
         best = torch.sort(best).values  # (kept states stay in child order: the next depth's child indices are deterministic)
-        parent, k = parent[best], k[best]
+        parent = parent[best]
         counts.append((M * K, int(idx.numel()), int(best.numel())))
         if best.numel() == 0:
             break
         src_next = src.index_select(0, parent)
-        frontier, _, _ = venv.transition(frontier.index_select(0, parent), {form: pay.index_select(0, k), "operation": op.index_select(0, k)},
+        frontier, _, _ = venv.transition(frontier.index_select(0, parent), {form: step_pay.index_select(0, best), "operation": step_op.index_select(0, best)},
                                          src_next)
-        path = torch.cat([path.index_select(0, parent), k.reshape(-1, 1)], 1)
+        path = torch.cat([path.index_select(0, parent), step.index_select(0, best)], 1)
         root, src = root.index_select(0, parent), src_next
     return BeamResult(None, counts, None)
+
+
+# ---- the objects of a grid as candidate actions ------------------------------------------------------------------------------------
+def components_numpy(grid, grid_dim, max_components, skip_color=-1):
+    """The connected components of ONE grid as arcle_components_rows reports them (include/arcle_hip.h) — the host mirror the tests
+    pin the device against, and pin against the reference's `dfs` (color.py:8-30): 4-connected cells of the same colour inside
+    grid_dim, in ascending row-major index of their first cell (the seed); cells of `skip_color` (-1: none) belong to no component.
+    grid int8 [H, W]; -> (count, left, comp int32 [C, 8] = x0, y0, x1, y1, sx, sy, colour, cells (rows >= count zero),
+    masks uint8 [C, H, W]), left = the cells inside grid_dim, not of skip_color, in no written component."""
+    grid = np.asarray(grid)
+    H, W = grid.shape
+    gh, gw = min(int(grid_dim[0]), H), min(int(grid_dim[1]), W)
+    C = int(max_components)
+    todo = np.zeros((H, W), bool)
+    todo[:gh, :gw] = True
+    if skip_color >= 0:
+        todo &= grid.astype(np.int64) != ((int(skip_color) + 128) % 256 - 128)
+    comp, masks, n = np.zeros((C, 8), np.int32), np.zeros((C, H, W), np.uint8), 0
+    for sx in range(gh):
+        for sy in range(gw):
+            if not todo[sx, sy] or n >= C:
+                continue
+            col = grid[sx, sy]
+            queue, cells = collections.deque([(sx, sy)]), []
+            todo[sx, sy] = False
+            while queue:
+                x, y = queue.popleft()
+                cells.append((x, y))
+                for xn, yn in ((x - 1, y), (x + 1, y), (x, y - 1), (x, y + 1)):
+                    if 0 <= xn < gh and 0 <= yn < gw and todo[xn, yn] and grid[xn, yn] == col:
+                        todo[xn, yn] = False
+                        queue.append((xn, yn))
+            xs, ys = np.array(cells).T
+            masks[n, xs, ys] = 1
+            comp[n] = (xs.min(), ys.min(), xs.max(), ys.max(), sx, sy, int(col), len(cells))
+            n += 1
+    return n, int(todo.sum()), comp, masks
+
+
+def object_actions(comp, box_ops, seed_ops):
+    """The components of M states (`ARCVecEnv.components`: count [M], box [M, C, 4], seed [M, C, 2]) as a candidate set per state:
+    {"bbox": int32 [M, K, 4], "operation": int32 [M, K]}, K = C * (len(box_ops) + len(seed_ops)).  Component k contributes its box
+    with every op of box_ops (Move / Rotate / Flip / Copy want the box of a shape), then its seed as the 1 x 1 box (sx, sy, sx, sy)
+    with every op of seed_ops (a 1 x 1 rectangle is what FloodFill accepts).  The slots of components k >= count get operation -1:
+    expansion reports ARCLE_ST_BAD_OP for such a child alone, and beam_search drops children with a status bit.  Pure indexing on the
+    device: no host synchronisation."""
+    box, seed, count = comp.box, comp.seed, comp.count
+    M, C = int(box.shape[0]), int(box.shape[1])
+    dev = box.device
+    ops = torch.as_tensor(list(box_ops) + list(seed_ops), dtype=torch.int32, device=dev)
+    nb, ns = len(box_ops), len(seed_ops)
+    per = nb + ns
+    bb = torch.cat([box.reshape(M, C, 1, 4).expand(M, C, nb, 4), torch.cat([seed, seed], 2).reshape(M, C, 1, 4).expand(M, C, ns, 4)], 2)
+    there = (torch.arange(C, device=dev).reshape(1, C) < count.reshape(M, 1)).reshape(M, C, 1)
+    op = torch.where(there, ops.reshape(1, 1, per), torch.full((), -1, dtype=torch.int32, device=dev))
+    bb = torch.where(there.reshape(M, C, 1, 1), bb.to(torch.int32), torch.zeros((), dtype=torch.int32, device=dev))  # (entries >= count were never written)
+    return {"bbox": bb.reshape(M, C * per, 4).contiguous(), "operation": op.reshape(M, C * per).to(torch.int32).contiguous()}
+
+
+def propose_objects(box_ops, seed_ops, max_components=16, skip_color=0):
+    """A `propose` for beam_search: at every depth the connected components of each frontier state's grid (`venv.components`, one
+    launch) with box_ops on their boxes and seed_ops on their seeds (`object_actions`)."""
+    box_ops, seed_ops = list(box_ops), list(seed_ops)
+
+    def propose(venv, rows):
+        return object_actions(venv.components(rows, max_components=max_components, skip_color=skip_color), box_ops, seed_ops)
+    return propose

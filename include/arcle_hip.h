@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ARCLE_ABI_VERSION 7
+#define ARCLE_ABI_VERSION 8
 #define ARCLE_MAX_OPS 64
 #define ARCLE_MAX_CELLS 1024 /* H*W <= 1024: one 64-lane wavefront x 16 cells holds a plane (the one-wavefront-per-env kernels);
                                 larger planes (H, W <= 127) are served by the workgroup-per-env kernels — see "Grids beyond
@@ -479,6 +479,23 @@ int arcle_expand_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_
                       const void* sel, const int32_t* op, int32_t action_row_stride, const int32_t* src_env, int32_t* reward,
                       uint8_t* term, uint8_t* status, uint64_t* hash, int32_t* dense, uint64_t* parent_hash, uint32_t flags,
                       void* stream);
+/* Connected components (color.py:8-30: 4-connected, same colour, inside grid_dim) of the grid of every state row, each as a ready-made
+ * BBoxWrapper / PointWrapper action: what a search proposes its candidate actions from (arcle_expand_rows takes a set per row).
+ * rows == NULL: the resident envs 0 .. n_rows-1 (n_rows <= n_envs); else rows as for arcle_hash_rows (any alignment, stride >= the
+ * row length); only the grid segment and grid_dim of a row are read.
+ *   count int32 [n_rows][2] = (written, left)
+ *   comp  int32 [n_rows][max_comp][8] = x0, y0, x1, y1, sx, sy, colour, cells
+ *   bits  optional uint8 [n_rows][max_comp][arcle_mask_bits_stride()]: the component's cells in the layout of arcle_step_bits /
+ *         arcle_pack_mask_bits (bit f & 7 of byte f >> 3, f = row * W + col)
+ * Components come in ascending row-major index of their first cell, sx * W + sy; that cell is the seed: a valid PointWrapper action
+ * and a FloodFill seed.  (x0, y0, x1, y1) is the inclusive bounding box in BBoxWrapper's order (rows x, columns y).  skip_color: -1
+ * skips nothing; otherwise cells of that colour belong to no component (0: ARC's background).  left = the cells inside grid_dim, not
+ * of skip_color, that are in no written component: 0 <=> the list is complete.  Entries k >= written are not written at all.
+ * No side effects: the handle's resident state, sticky status, counters, dense cache and installed outputs are untouched.  Refusals
+ * as arcle_hash_rows (more than ARCLE_MAX_CELLS cells per plane: ARCLE_ERR_CONFIG); max_comp outside [1, ARCLE_MAX_CELLS], a stride
+ * below the row length or rows == NULL with n_rows > n_envs: ARCLE_ERR_ARG.  One wavefront per row; allocates nothing: may be captured. */
+int arcle_components_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, int32_t skip_color,
+                          int32_t* count, int32_t* comp, uint8_t* bits, void* stream);
 /* One state plane as a dense [n_envs][H*W] int8 array (device or pinned host memory), a strided copy on the stream: the
  * get_state()/set_state() of single keys of the reference's state dict. */
 int arcle_get_plane(arcle_env* env, int plane, int8_t* dst, void* stream);
