@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("ARCLE_HIP_LIB") or os.path.join(_CSRC, "libarcle_hip.
 # two translation units: the one-wavefront-per-env kernels + the C ABI (arcle_hip.hip <- arcle_wave.h) and the workgroup-per-env kernels
 # for grids of more than 1024 cells (arcle_big.hip <- arcle_big.h); arcle_big_params.h is shared
 UNITS = [os.path.join(_CSRC, "arcle_hip.hip"), os.path.join(_CSRC, "arcle_big.hip")]
-SOURCES = UNITS + [os.path.join(_CSRC, "arcle_wave.h"), os.path.join(_CSRC, "arcle_search.h"), os.path.join(_CSRC, "arcle_components.h"), os.path.join(_CSRC, "arcle_big.h"), os.path.join(_CSRC, "arcle_big_params.h"),
+SOURCES = UNITS + [os.path.join(_CSRC, "arcle_wave.h"), os.path.join(_CSRC, "arcle_group.h"), os.path.join(_CSRC, "arcle_search.h"), os.path.join(_CSRC, "arcle_components.h"), os.path.join(_CSRC, "arcle_big.h"), os.path.join(_CSRC, "arcle_big_params.h"),
                    os.path.join(_CSRC, "..", "..", "include", "arcle_hip.h")]
 
 ABI_VERSION = 8

@@ -202,9 +202,17 @@ ARCLE_DEV int rare_v(int v) {  // (the same for a value held in a vector registe
 }
 __device__ __forceinline__ void sink_s(uint32_t v) { asm volatile("" ::"s"(v)); }
 __device__ __forceinline__ void sink_v(uint32_t v) { asm volatile("" ::"v"(v)); }
+// ---- what arcle::deal_group (arcle_group.h) needs beyond the above ----
+ARCLE_DEV uint32_t umulhi(uint32_t a, uint32_t b) { return __umulhi(a, b); }
+ARCLE_DEV uint32_t umin(uint32_t a, uint32_t b) { return __builtin_elementwise_min(a, b); }
+ARCLE_DEV uint32_t mbcnt_lo(uint32_t mask, uint32_t base) { return __builtin_amdgcn_mbcnt_lo(mask, base); }  // base + popc(mask & lanes below this one), lanes 0-31
+ARCLE_DEV bool inverse_ballot(uint64_t mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }          // this lane's bit of a wave-uniform mask
+// "these argument-block fields are wanted": their fetch is issued where this stands (no instruction of its own)
+ARCLE_DEV void touch_args(const void* a, const void* b) { asm volatile("" ::"s"(a), "s"(b)); }
 }  // namespace xl
 
 #include "arcle_wave.h"
+#include "arcle_group.h"       // the deal of a self-ordering launch: slot -> env and its inputs (arcle::deal_group)
 #include "arcle_search.h"      // state hash + K-actions-per-row expansion (arcle_hash_rows / arcle_expand_rows)
 #include "arcle_components.h"  // connected components of a row's grid as candidate actions (arcle_components_rows)
 #include "arcle_big_params.h"  // grids beyond ARCLE_MAX_CELLS: one workgroup per env (arcle_big.hip)
@@ -238,9 +246,7 @@ __device__ __forceinline__ int wave_of_launch(int waves_per_wg = WAVES_PER_WG, u
 // NEXT step's slots from a table written by the front workgroups of the previous launch (arcle_step_many, or single steps after
 // arcle_hint_next_ops: 4.93 us, but only for callers who know their ops one step ahead).  Round 5: the launch orders ITSELF inside groups
 // of ARCLE_GROUP_SIZE envs (the GROUPED block of arcle_step_kernel below: 4.90 us, no table, no hint) and the table form is gone.
-#ifndef ARCLE_GROUP_SIZE
-#define ARCLE_GROUP_SIZE 32  // envs (= dispatch strata) per group of a self-ordering launch
-#endif
+// (ARCLE_GROUP_SIZE: arcle_group.h)
 
 // ING: selection ingress form; FW: arcle::FW_* grid-width class;
 // ACCT: 1 = add the step's algorithmic bytes to p.acct[env]; FEAT: 1 = carries the ARCLE_STEP_FEATURE_FLAGS code
@@ -300,95 +306,16 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) __attribute__((amdgpu_num_sgpr(A
 #endif
   if constexpr (FL >= 0 && (FL & ARCLE_STEPX_GROUPED) != 0) {
     // ---- the launch that orders itself (round 5) ------------------------------------------------------------------------------------
-    // An XCD starts the workgroups of its slot range in index order, so the range falls into GS = 32 strata of G = rs / 32 consecutive slots
-    // that start one after the other.  Group g of the XCD = the 32 slots {g + j G, j = 0..31} (one per stratum) and the 32 CONTIGUOUS envs
-    // xbase + 32 g .. + 31.  Every wave of the group loads the inputs of ALL 32 envs — records, counters, tuples, op indices: one request of
-    // the whole wave per array, 1.4 KB — ballots which ops are object operations (m, L = popc(m)) and applies one rule inside
-    // the group: by default position j steps env j; the k-th object op found in a position >= L trades places with the k-th other op found
-    // in a position < L.  All 32 waves compute the same permutation from the same 32 ops, so every env is stepped exactly once whatever the
-    // ops are, and the slot's env is then picked out of the lanes with v_readlane: no table, no hint, no second round trip, no barrier.
-    // Measured (profiles/round5_experiments.txt): 8192 envs 5.37 -> 4.90 us per launch (the table form with hints: 4.93; ops dealt in the
-    // ideal order: 4.72); groups of 16: 5.00, of 64: 4.92; a group of 16 whose traded slots re-request their inputs (scalar loads): 5.25.
+    // The deal — slot coordinates -> the env this wave steps and that env's inputs — is arcle::deal_group (arcle_group.h, shared with the CPU
+    // emulator of tests/emu/group_emu.cpp).  The permutation inside a group of 32 envs is computed from launch-constant inputs only (the
+    // group's op indices), so all 32 waves of a group agree on it whenever they start.
     // Preloaded arguments of these launches: `order` carries the op table's 64-bit object-op mask, `n_envs` the reciprocal of G
     // (floor(2^32 / G) + 1; every slot holds an env: n_envs % 256 == 0, checked by the launcher), `nb8` the slots per XCD and `wpw_front`
     // the log2 of the waves per workgroup.
-    const uint64_t long_mask = (uint64_t)reinterpret_cast<uintptr_t>(order);
-    const uint32_t magic = (uint32_t)n_envs, rs = nb8;
-    constexpr uint32_t GS = ARCLE_GROUP_SIZE;
-    static_assert(GS == 32, "the lane layout below is written for groups of 32");
-    // (wave-uniform arithmetic on the vector ALUs — xl::tov — the CU's scalar unit is the short resource)
-    const uint32_t vb = xl::tov(blockIdx.x);
-    const uint32_t s_local = ((vb >> 3) << (uint32_t)wpw_front) + (threadIdx.x >> 6);
-    const uint32_t j = __umulhi(s_local, magic);  // stratum of this slot = its position in the group
-    // first env of the group: xcd rs + GS (s_local - j G), G = rs / GS
-    const uint32_t gfirst = (uint32_t)xl::mul24s(rs, (int)(vb & 7u) - (int)j) + (s_local << 5);
-    const uint32_t js = xl::uniform(j), gfirst_s = xl::uniform(gfirst);
+    const arcle::GroupSlot slot = arcle::group_slot_of_wave(blockIdx.x, threadIdx.x, (uint32_t)n_envs, nb8, (uint32_t)wpw_front);
     arcle::Wave w(p, &tiles[threadIdx.x >> 6], nullptr, (int)(threadIdx.x & 63), ING, FW, false, ACCT != 0, false);
-    static_assert(ING != arcle::INGRESS_BBOX5_PF, "grouped launches: tuples, 5-tuple records, masks — not the record-prefetching form");
-    constexpr bool REC5 = ING == arcle::INGRESS_BBOX5, CELLS = arcle::is_cells(ING);  // (masks / bit-packed masks: the payload is per cell — fetched for the slot's env once it is known)
-    constexpr bool BY_LIMIT = (FL & ARCLE_STEP_TRUNCATE) != 0;  // (the research step: an env about to be re-initialised counts as long: its auto-reset is that kernel's longest wave)
-    // the group's inputs: lanes 0-31 read the 32 op indices (the upper half repeats them); records (16 B per env), bbox tuples (16 B), point
-    // tuples and counters (8 B) as ONE contiguous block per array spread over the 64 lanes — env e's item in lanes 2 e, 2 e + 1
-    const uint32_t lane = threadIdx.x & 63u, e = lane & 31u;
-    const uint32_t vop = REC5 ? xl::load32(sel, 20u * (gfirst + e) + 16u) : xl::load32(op, (gfirst + e) << 2);
-    const xl::U2 vrec = xl::load8(rec, (gfirst << 4) + (lane << 3));
-    xl::U4 vsel = {0u, 0u, 0u, 0u};
-    if constexpr (CELLS) {
-    } else if constexpr (REC5) vsel = xl::load16u_at(sel, 20u * (gfirst + e));  // (records are only dword aligned; per lane e)
-    else if constexpr (ING == arcle::INGRESS_BBOX) {
-      const xl::U2 t = xl::load8(sel, (gfirst << 4) + (lane << 3));
-      vsel[0] = t[0], vsel[1] = t[1];
-    } else vsel[0] = xl::load32(sel, (gfirst << 3) + (lane << 2));
-    xl::U2 vcnt = {0u, 0u};
-    if constexpr (BY_LIMIT) vcnt = xl::load8(cnt, (gfirst + e) << 3);  // (per lane e: the classification reads env e's step counter)
-    else vcnt[0] = xl::load32(cnt, (gfirst << 3) + (lane << 2));
-    // (the fetch of the argument block — plane bases, op table — is issued HERE, beside the loads above, not behind the wait for the group's ops)
-    asm volatile("" ::"s"(pa.plane[ARCLE_PL_GRID]), "s"(pa.d_ops));
-    bool lg = ((long_mask >> __builtin_elementwise_min(vop, 63u)) & 1ull) != 0ull;
-    if constexpr (BY_LIMIT) lg = lg || (pa.step_limit > 0 && (int32_t)vcnt[0] == pa.step_limit - 1);
-    const uint64_t m = xl::ballot(lg) & 0xffffffffull;
-    const uint64_t hi = xl::ballot(lane >= (uint32_t)__builtin_popcountll(m));  // positions >= L, as a lane compare
-    const uint64_t late_long = m & hi, early_other = ~(m | hi);                 // the two sides of the trade, k-th with k-th
-    const uint32_t ra = __builtin_amdgcn_mbcnt_lo((uint32_t)late_long, 0u), rb = __builtin_amdgcn_mbcnt_lo((uint32_t)early_other, 0u);
-    // code: what a position is (0x40 | rank: a late object op, 0x80 | rank: an early other op, 0x100 | lane: it keeps its env); want: the code of
-    // the position whose env it steps (the k-th of the other side, or itself) — found with ONE ballot, no branch
-    uint32_t code = 0x100u | lane;
-    code = __builtin_amdgcn_inverse_ballot_w64(late_long) ? (0x40u | ra) : code;
-    code = __builtin_amdgcn_inverse_ballot_w64(early_other) ? (0x80u | rb) : code;
-    const uint32_t want = (code & 0x100u) ? code : (code ^ 0xc0u);
-    const int pos = __builtin_ctzll(xl::ballot(code == xl::readlane(want, (int)js)));
-    const int my_env = (int)gfirst_s + pos;
-    // the env's scalars out of the lanes that hold them; an item that spans two lanes has its upper words moved to the even lane first (DPP),
-    // so that ONE lane index serves every v_readlane of the array (no scalar index arithmetic)
     arcle::StepInputs in;
-    const int h = pos << 1;
-    in.rec[0] = xl::readlane(vrec[0], h);
-    in.rec[1] = xl::readlane(vrec[1], h);
-    in.rec[2] = xl::readlane(xl::quad_bcast_odd(vrec[0]), h);
-    in.rec[3] = xl::readlane(xl::quad_bcast_odd(vrec[1]), h);
-    if constexpr (CELLS) {
-      in.payload = arcle::load_payload(w, my_env, 0, sel);
-    } else if constexpr (REC5) {
-#pragma unroll
-      for (int k = 0; k < 4; k++) in.payload[k] = xl::readlane(vsel[k], pos);
-    } else if constexpr (ING == arcle::INGRESS_BBOX) {
-      in.payload[0] = xl::readlane(vsel[0], h);
-      in.payload[1] = xl::readlane(vsel[1], h);
-      in.payload[2] = xl::readlane(xl::quad_bcast_odd(vsel[0]), h);
-      in.payload[3] = xl::readlane(xl::quad_bcast_odd(vsel[1]), h);
-    } else {
-      in.payload = arcle::u4_zero();
-      in.payload[0] = xl::readlane(vsel[0], h);
-      in.payload[1] = xl::readlane(xl::quad_bcast_odd(vsel[0]), h);
-    }
-    if constexpr (BY_LIMIT) {
-      in.cnt[0] = xl::readlane(vcnt[0], pos);
-      in.cnt[1] = xl::readlane(vcnt[1], pos);
-    } else {
-      in.cnt[0] = xl::readlane(vcnt[0], h);
-      in.cnt[1] = xl::readlane(xl::quad_bcast_odd(vcnt[0]), h);
-    }
-    in.op = xl::readlane(vop, pos);
+    const int my_env = arcle::deal_group<ING>(w, slot, threadIdx.x, (uint64_t)reinterpret_cast<uintptr_t>(order), rec, cnt, op, sel, pa.plane[ARCLE_PL_GRID], pa.d_ops, in);
     arcle::wave_step<ING, FW, ACCT, FEAT, FL>(w, my_env, in, 0, 0, false, arcle::u4_zero());
 #ifdef ARCLE_TRACE_WAVES  // (diagnostic builds, tools/launchtrace.py: when this wave entered and left, into the launch's half of the trace buffer)
     if (pa.acct && (threadIdx.x & 63u) == 0) {
@@ -1134,6 +1061,8 @@ static constexpr int RESEARCH_INC_FL = RESEARCH_FL | ARCLE_STEP_ROWS_INCREMENTAL
 //   rollout   arcle_rollout_kernel<ING, FW_FAST, 30, FL>; rows with FEAT 1: arcle_rollout_feat_kernel<ING, FW_FAST, 30, FL> (arcle_rollout_ex)
 // A launch takes the first row that matches its flags (-1: a step without feature flags, any rollout) and has a twin that applies, in the
 // order prefetch, grouped, stream, plain.  The flag sets are distinct and -1 comes last, so the lookups of plan_launch (lean_twin) agree.
+// (Every grouped twin, RESEARCH_INC_FL's too, orders by op index alone.  An env about to be re-initialised — step counter at limit - 1 — is
+// that kernel's longest wave, but the counters are written by the launch's own waves and cannot be part of the order: arcle_group.h, INVARIANT.)
 // Development builds (-DARCLE_FAST_BUILD: seconds instead of minutes) keep the cells marked DEV, for bbox tuples only, and of the kernels
 // outside the table the feature / accounting one of the 30 x 30 grid.
 #ifdef ARCLE_FAST_BUILD

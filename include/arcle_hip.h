@@ -302,8 +302,9 @@ int arcle_step_many(arcle_env* env, int ingress, int32_t n_steps, const void* se
  * the flag set ARCLE_STEP_AUTORESET | ARCLE_STEP_ELIDE_SELECTED; the tuple forms also with ARCLE_STEP_ELIDE_SELECTED alone (no auto-reset);
  * bbox / bbox5 also with ARCLE_STEP_AUTORESET | _ELIDE_SELECTED | _PACK_OBS or the research env's set with incremental FilterO2ARC rows; n_envs a multiple of 256 in [2304, 10240], actions in DEVICE memory, an op table with object operations, no byte
  * accounting.  Waves of a group of 32 consecutive envs read the group's 32 actions and permute the group among their 32 dispatch slots
- * (arcle_step_kernel, GROUPED).  Scheduling only: every env is stepped exactly once whatever the operations are; results, outputs and
- * their layout are those of the plain launch.  No tables, no extra memory, nothing to allocate before a stream capture.
+ * (arcle_step_kernel, GROUPED; arcle_group.h).  The permutation is computed from launch-constant inputs only (the group's operation indices
+ * and the op table: nothing a wave of the launch writes), so the 32 waves agree on it whenever each of them starts.  Scheduling only: every
+ * env is stepped exactly once whatever the operations are; results, outputs and their layout are those of the plain launch.  No tables, no extra memory, nothing to allocate before a stream capture.
  * arcle_set_dispatch_order(env, 0) turns it off for the handle (default on).
  * arcle_hint_next_ops: ABI 4's one-shot hint of the NEXT step's operations (the table form of ordered dispatch needed them a step
  * ahead).  Still accepted and validated — stride 1 for op arrays, 5 for the op field of BBoxWrapper records — and ignored. */

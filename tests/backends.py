@@ -239,8 +239,9 @@ class EmuBackend:
 
     def set_task_table(self, inputs, answers):
         T = len(inputs)
-        self.tbl = [np.zeros((T, self.PS), np.int8), np.zeros((T, 2), np.int8), np.zeros((T, self.PS), np.int8),
-                    np.zeros((T, 2), np.int8)]
+        # (the dims arrays are allocated in whole dwords, as arcle_set_task_table asks: an entry's two dims are read with one aligned dword load)
+        dims = lambda: np.zeros(((T + 1) & ~1, 2), np.int8)[:T]
+        self.tbl = [np.zeros((T, self.PS), np.int8), dims(), np.zeros((T, self.PS), np.int8), dims()]
         for j, (a, b) in enumerate(zip(inputs, answers)):
             self.tbl[0][j, :self.P].reshape(self.H, self.W)[:a.shape[0], :a.shape[1]] = a
             self.tbl[2][j, :self.P].reshape(self.H, self.W)[:b.shape[0], :b.shape[1]] = b

@@ -137,9 +137,6 @@ def info_equal(a, b):
 def test_vec_env_research_rollout_matches_step_bbox_8192():
     N, T = 8192, 32
     v, tw = research_env(N), research_env(N)
-    # the twin steps with plain launches: at 8192 envs the self-ordering launch (arcle_set_dispatch_order) is otherwise planned, and its
-    # results were seen to differ from plain launches on a GPU shared with other processes — a question of that launch, not of rollouts
-    tw.batch.set_dispatch_order(False)
     tw.enable_flat_rows(filtered=True)
     v.enable_flat_rows(filtered=True)
     desync([v], N)

@@ -123,7 +123,7 @@ def test_grouped_step_many_and_hints_match_single_steps():
 
 def test_grouped_research_step_matches_ungrouped():
     """The research env's flag set (dense reward, TimeLimit, device-drawn augmented tasks, incremental FilterO2ARC rows): the grouped launch
-    also counts an env about to be re-initialised as a long wave (its step counter reads limit - 1) — identical to the ungrouped twin."""
+    (ordered by op index alone, like every other) — identical to the ungrouped twin."""
     import torch
     import bench
     from arcle_amd.envs import ARCVecEnv, O2ARCv2Env
@@ -146,6 +146,47 @@ def test_grouped_research_step_matches_ungrouped():
     for k in va.batch.planes:
         assert torch.equal(va.batch.planes[k], vb.batch.planes[k]), k
     assert torch.equal(va.batch.cnt, vb.batch.cnt)
+    va.check_errors(), vb.check_errors()
+
+
+@pytest.mark.parametrize("form", ["bbox", "bbox5"])
+def test_research_step_beyond_one_occupancy_round_matches_plain_launches(form):
+    """16384 envs are more waves than the device holds at once, so the early and the late slots of a group are never co-resident: a late wave
+    finds the counters the early ones stored.  TimeLimit 4 with the episodes desynchronised over 0..3 keeps envs at limit - 2 or
+    limit - 1 in the groups at every step — the states a classification by step counter trips over (tests/test_group_emu.py runs the same
+    configuration slot by slot on the CPU).  Rewards, flags, rows, every plane and the counters against the twin with plain launches."""
+    import torch
+    from arcle_amd.envs import ARCVecEnv, O2ARCv2Env
+    from arcle_amd.loaders import SyntheticLoader
+    n, K, limit, dev = 16384, 12, 4, torch.device("cuda:0")
+    bb_np, op_np = _streams(K, n, 41)
+    bb, op = torch.from_numpy(bb_np).to(dev), torch.from_numpy(op_np % 35).to(dev)
+    act5 = torch.cat([bb, op[:, :, None]], 2).contiguous()
+    kw = dict(device=dev, seed=5, autoreset="resample", augment=("permute", "rot90"), dense_reward=True, max_episode_steps=limit)
+    with _Env(ARCLE_GROUPED=0):
+        va = ARCVecEnv(O2ARCv2Env, n, SyntheticLoader(n_tasks=60, seed=2, max_size=(30, 30)), **kw)
+    with _Env(ARCLE_GROUPED=1, ARCLE_GROUP_MIN=0, ARCLE_GROUP_MAX=10000000):
+        vb = ARCVecEnv(O2ARCv2Env, n, SyntheticLoader(n_tasks=60, seed=2, max_size=(30, 30)), **kw)
+    steps = torch.randint(0, limit, (n,), generator=torch.Generator().manual_seed(1), dtype=torch.int32)
+    # (a condition on the inputs: the draw puts every phase 0..3 into every group — a counter runs 0, 1, .., limit and starts over, so
+    # whatever the step, a group then holds an env at limit - 2 or limit - 1 unless terminations moved all of them)
+    assert all(bool((steps.reshape(-1, 32) == c).any(1).all()) for c in range(limit))
+    steps = steps.to(dev)
+    for v in (va, vb):
+        v.reset()
+        v.enable_flat_rows(filtered=True)
+        v.batch.cnt[:, 0] = steps  # desynchronised episodes
+        v._refresh_rows()
+    assert not va.batch.launch_info(form, va.flags)["orders_itself"] and vb.batch.launch_info(form, vb.flags)["orders_itself"]
+    for s in range(K):
+        _, ra, ta, tra, _ = va.step_bbox5(act5[s]) if form == "bbox5" else va.step_bbox(bb[s], op[s])
+        _, rb, tb, trb, _ = vb.step_bbox5(act5[s]) if form == "bbox5" else vb.step_bbox(bb[s], op[s])
+        assert torch.equal(ra, rb) and torch.equal(ta, tb) and torch.equal(tra, trb), (form, s)
+        assert torch.equal(va.rows, vb.rows), (form, s)
+        assert torch.equal(va.batch.cnt, vb.batch.cnt), (form, s)
+    for k in va.batch.planes:
+        assert torch.equal(va.batch.planes[k], vb.batch.planes[k]), (form, k)
+    assert torch.equal(va.batch.rec, vb.batch.rec) and torch.equal(va.batch.episode, vb.batch.episode)
     va.check_errors(), vb.check_errors()
 
 
