@@ -16,7 +16,7 @@ UNITS = [os.path.join(_CSRC, "arcle_hip.hip"), os.path.join(_CSRC, "arcle_big.hi
 SOURCES = UNITS + [os.path.join(_CSRC, "arcle_wave.h"), os.path.join(_CSRC, "arcle_group.h"), os.path.join(_CSRC, "arcle_search.h"), os.path.join(_CSRC, "arcle_components.h"), os.path.join(_CSRC, "arcle_big.h"), os.path.join(_CSRC, "arcle_big_params.h"),
                    os.path.join(_CSRC, "..", "..", "include", "arcle_hip.h")]
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 N_PLANES = 8
 MAX_OPS = 64
 BITS_STRIDE = 128  # bytes between envs of a bit-packed mask array (ARCLE_MAX_CELLS / 8)
@@ -96,7 +96,14 @@ def lib():
         raise ArcleHipError(
             f"{LIB_PATH} is missing — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  arcle_amd has no CPU fallback.")
-    L = ctypes.CDLL(LIB_PATH)
+    _lib = load(LIB_PATH, ABI_VERSION)
+    return _lib
+
+
+def load(path, abi_version=None):
+    """dlopens the library at `path` and declares its entry points; abi_version None accepts whatever the file reports (measurement
+    tools that run a second build — an older commit's — beside the current one: tools/expandbitsbench.py)."""
+    L = ctypes.CDLL(path)
     vp, u32, i32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32
     L.arcle_abi_version.restype = ctypes.c_int
     L.arcle_create.argtypes = [ctypes.POINTER(Config), ctypes.POINTER(Buffers), ctypes.POINTER(vp)]
@@ -151,7 +158,6 @@ def lib():
                                        ctypes.c_int, vp]
     L.arcle_last_error.argtypes = [vp]
     L.arcle_last_error.restype = ctypes.c_char_p
-    if L.arcle_abi_version() != ABI_VERSION:
+    if abi_version is not None and L.arcle_abi_version() != abi_version:
         raise ArcleHipError("libarcle_hip.so ABI version mismatch — rebuild")
-    _lib = L
     return L

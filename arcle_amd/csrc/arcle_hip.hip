@@ -657,7 +657,10 @@ static int need_rule_planes(arcle_env* e, int ingress, uint32_t flags) {  // (th
   return ARCLE_OK;
 }
 static int need_rule_mask(arcle_env* e, int ingress, uint32_t flags) {  // (the row kernels: no `selected` plane to ask for, rows carry it)
-  return (flags & ARCLE_STEP_CONTINUE_RULE) && ingress != arcle::INGRESS_MASK ? fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_CONTINUE_RULE needs mask ingress") : ARCLE_OK;
+  return (flags & ARCLE_STEP_CONTINUE_RULE) && !arcle::is_cells(ingress) ? fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_CONTINUE_RULE needs mask ingress (int8 masks or bit rows)") : ARCLE_OK;
+}
+static int need_bits_aligned(arcle_env* e, const void* bits) {  // (a lane reads its 16 cells as one uint16)
+  return (reinterpret_cast<uintptr_t>(bits) & 1) ? fail(e, ARCLE_ERR_ARG, "bit-packed mask rows must be 2-byte aligned") : ARCLE_OK;
 }
 static int need_steps(arcle_env* e, int32_t n_steps) { return n_steps > 0 ? ARCLE_OK : fail(e, ARCLE_ERR_ARG, "n_steps must be positive"); }
 static int need_src_env(arcle_env* e, int32_t n_rows, const int32_t* src_env) {
@@ -1179,7 +1182,10 @@ static int launch_step_tbl(bool acct, bool feat, dim3 g, dim3 b, hipStream_t st,
 // is the same question for the caller's argument check).  FULL: the caller's kernels have FW_FULL instantiations of their own (the step
 // kernels); those that keep the planes in registers have not — lane predication does not matter there, FW_FULL shares FW_FAST's code.
 static constexpr bool takes(uint32_t forms, int ingress) { return ingress >= 0 && ingress <= arcle::INGRESS_BITS && ((forms >> ingress) & 1u); }
-static constexpr uint32_t ROW_FORMS = I_MASK | I_BBOX | I_POINT;  // rollouts, arcle_transition_rows
+static constexpr uint32_t ROW_FORMS = I_MASK | I_BBOX | I_POINT;  // rollouts
+static constexpr uint32_t I_BITS = 1u << arcle::INGRESS_BITS;
+static constexpr uint32_t TRANSITION_FORMS = ROW_FORMS | I_BITS;   // arcle_transition_rows (bit rows: grids of at most ARCLE_MAX_CELLS cells)
+static constexpr uint32_t EXPAND_FORMS = I_BBOX | I_POINT | I_BITS;  // arcle_expand_rows
 template <uint32_t FORMS, bool FULL, int ING = 0, class F>
 static int with_form(int ingress, int fw, F&& f) {
   if constexpr (ING > arcle::INGRESS_BITS) return ARCLE_ERR_ARG;
@@ -1930,7 +1936,11 @@ extern "C" int arcle_transition_rows(arcle_env* e, int32_t n_rows, const int8_t*
   const int len = arcle::flat_obs_len(e->base, 0);
   if ((out_stride & 15) || (reinterpret_cast<uintptr_t>(rows_out) & 15) || out_stride < ((len + 15) & ~15) + (tail ? 16 : 0))
     return fail(e, ARCLE_ERR_ARG, "output rows: 16-byte aligned, stride a multiple of 16 >= the row length (+16 with a tail)");
-  if (!takes(ROW_FORMS, ingress)) return fail(e, ARCLE_ERR_ARG, "arcle_transition_rows takes mask, bbox or point selections");  // (before any allocation or launch)
+  if (!takes(TRANSITION_FORMS, ingress)) return fail(e, ARCLE_ERR_ARG, "arcle_transition_rows takes mask, bit-row, bbox or point selections");  // (before any allocation or launch)
+  if (ingress == arcle::INGRESS_BITS) {
+    if (e->big) return fail(e, ARCLE_ERR_ARG, "arcle_transition_rows: bit rows on handles of at most 1024 cells per plane (ARCLE_MAX_CELLS) only");
+    if (int rc = need_bits_aligned(e, sel)) return rc;
+  }
   DeviceGuard guard(e->device);
   if (e->big) {
     // the state does not fit a wavefront, so the stateless transition is three launches over SCRATCH envs (one per row): rows -> scratch
@@ -1978,7 +1988,7 @@ extern "C" int arcle_transition_rows(arcle_env* e, int32_t n_rows, const int8_t*
   // in place: a plane the op did not touch stays where it is (the writer's incremental mode); otherwise it is passed through
   if (rows_out == rows_in && out_stride == in_stride) p.flags |= ARCLE_STEP_ROWS_INCREMENTAL;
   const dim3 g = grid_for(n_rows), b(64 * WAVES_PER_WG);
-  with_form<ROW_FORMS, false>(ingress, width_class(e->base), [&](auto ing, auto fw) {
+  with_form<TRANSITION_FORMS, false>(ingress, width_class(e->base), [&](auto ing, auto fw) {
     hipLaunchKernelGGL((arcle_transition_rows_kernel<decltype(ing)::value, decltype(fw)::value>), g, b, 0, (hipStream_t)stream, p);
     return ARCLE_OK;
   });
@@ -2029,7 +2039,9 @@ extern "C" int arcle_expand_rows(arcle_env* e, int32_t n_rows, const int8_t* row
   if (n_rows <= 0 || n_actions <= 0) return fail(e, ARCLE_ERR_ARG, "n_rows and n_actions must be positive");
   if (action_row_stride != 0 && action_row_stride != n_actions)
     return fail(e, ARCLE_ERR_ARG, "action_row_stride: 0 (one action set for every row) or n_actions (a set per row)");
-  if (!takes(I_BBOX | I_POINT, ingress)) return fail(e, ARCLE_ERR_ARG, "arcle_expand_rows takes bbox or point selections");
+  if (!takes(EXPAND_FORMS, ingress)) return fail(e, ARCLE_ERR_ARG, "arcle_expand_rows takes bbox, point or bit-row selections");
+  if (ingress == arcle::INGRESS_BITS)
+    if (int rc = need_bits_aligned(e, sel)) return rc;
   if (e->big) return fail(e, ARCLE_ERR_CONFIG, "arcle_expand_rows: handles of at most 1024 cells per plane (ARCLE_MAX_CELLS); larger grids expand through arcle_transition_rows");
   if (int rc = need_src_env(e, n_rows, src_env)) return rc;
   if ((int64_t)n_rows * n_actions >= (1ll << 28)) return fail(e, ARCLE_ERR_ARG, "too many children (n_rows * n_actions < 2^28)");
@@ -2062,7 +2074,7 @@ extern "C" int arcle_expand_rows(arcle_env* e, int32_t n_rows, const int8_t* row
   x.hash = hash;
   x.parent_hash = parent_hash;
   const dim3 g = grid_for(n_rows * x.n_chunks), b(64 * WAVES_PER_WG);
-  with_form<I_BBOX | I_POINT, false>(ingress, width_class(e->base), [&](auto ing, auto fw) {
+  with_form<EXPAND_FORMS, false>(ingress, width_class(e->base), [&](auto ing, auto fw) {
     hipLaunchKernelGGL((arcle_expand_kernel<decltype(ing)::value, decltype(fw)::value>), g, b, 0, (hipStream_t)stream, x);
     return ARCLE_OK;
   });

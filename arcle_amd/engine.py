@@ -563,7 +563,7 @@ class EnvBatch:
     def transition_rows(self, rows, form, payload, op, src_env=None, out=None, tail=False, flags=0, reward=None, term=None):
         """`transition(state, action)` of the reference (o2arcenv.py:149-151) for a batch of M (state row, action) pairs, none of
         which touches the resident envs: rows int8 [M, >= L]; payload in the ingress form `form` ("mask" int8 [M,H,W] | "bbox" int32
-        [M,4] | "point" int32 [M,2]); op int32 [M]; src_env int32 [M] = the resident env whose answer a Submit / the reward compares
+        [M,4] | "point" int32 [M,2] | "bits" uint8 [M,128]: bit-packed masks in `step_bits`' layout); op int32 [M]; src_env int32 [M] = the resident env whose answer a Submit / the reward compares
         with (None: env r for row r).  Returns (rows_out [M, stride], reward int32 [M], terminated uint8 [M]); with tail=True the last
         16 bytes of every output row carry (reward, 1, submit counted, terminated | status << 16).  All arrays device or pinned host."""
         M = int(rows.shape[0])
@@ -575,6 +575,8 @@ class EnvBatch:
         assert out.dim() == 2 and out.shape[0] == M and out.shape[1] >= stride and out.shape[1] % 16 == 0 and out.dtype == torch.int8 and out.is_contiguous()
         stride = out.shape[1]
         assert rows.dtype == torch.int8 and rows.stride(1) == 1 and payload.is_contiguous() and op.dtype == torch.int32 and op.is_contiguous()
+        if form == "bits":
+            assert payload.dtype == torch.uint8 and tuple(payload.shape) == (M, self.bits_stride)
         if reward is None:
             reward = torch.empty(M, dtype=torch.int32, device=self.device)
         if term is None:
@@ -598,18 +600,18 @@ class EnvBatch:
         return out
 
     def expand_rows(self, rows, form, payload, op, src_env=None, dense=False, flags=0, out=None):
-        """K candidate actions per state row, verdicts only (arcle_expand_rows): rows int8 [M, >= L], read only; form "bbox" | "point";
-        payload int32 [K, 4 | 2] with op int32 [K] (ONE action set applied to every row) or [M, K, 4 | 2] with op [M, K] (a set per
-        row); src_env int32 [M] = the env whose answer row m is judged against (None: env m).  Returns an Expansion of device tensors,
+        """K candidate actions per state row, verdicts only (arcle_expand_rows): rows int8 [M, >= L], read only; form "bbox" | "point" |
+        "bits"; payload int32 [K, 4 | 2] — "bits": uint8 [K, 128], bit-packed masks in `step_bits`' layout, what `components_rows(bits=
+        True)` writes — with op int32 [K] (ONE action set applied to every row) or [M, K, ...] with op [M, K] (a set per row); src_env int32 [M] = the env whose answer row m is judged against (None: env m).  Returns an Expansion of device tensors,
         all [M, K, ...]: reward int32, term uint8, status uint8 (ARCLE_ST_* bits of that child), hash int64 [M, K, 2] (state_hash,
         grid_hash of the child row, which is never written), dense int32 [M, K, 2] (correct, total) or None, parent_hash int64 [M, 2].
         Every value equals what transition_rows + hash_rows report for the replicated (row, action) pairs.  out: an Expansion of a
         previous call with the same shapes to write into (captured graphs)."""
-        assert form in ("bbox", "point"), "expand_rows takes bbox or point actions"
+        assert form in ("bbox", "point", "bits"), "expand_rows takes bbox, point or bits actions"
         M = int(rows.shape[0])
-        tw = 4 if form == "bbox" else 2
+        tw = {"bbox": 4, "point": 2, "bits": self.bits_stride}[form]
         assert rows.dtype == torch.int8 and rows.dim() == 2 and rows.stride(1) == 1
-        assert payload.dtype == torch.int32 and payload.is_contiguous() and op.dtype == torch.int32 and op.is_contiguous()
+        assert payload.dtype == (torch.uint8 if form == "bits" else torch.int32) and payload.is_contiguous() and op.dtype == torch.int32 and op.is_contiguous()
         if payload.dim() == 2:
             K, stride = int(payload.shape[0]), 0
             assert tuple(payload.shape) == (K, tw) and tuple(op.shape) == (K,)

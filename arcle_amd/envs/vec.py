@@ -548,8 +548,8 @@ class ARCVecEnv:
     def transition(self, rows, action, src_env=None, out=None, in_place=False):
         """The reference's `transition(state, action)` (o2arcenv.py:149-151; README: `env.transition(deepcopy(state), action)`) for
         a batch: rows int8 [M, L] = M states (as `state_rows` / a previous `transition` returns them — M is NOT tied to num_envs),
-        action = {"selection": [M,H,W] mask | "bbox": int32 [M,4] | "point": int32 [M,2], "operation": int32 [M]}; src_env int32
-        [M] = the env whose task (answer) row m belongs to (default: env m).  Returns (rows_out [M, L], reward int32 [M], terminated
+        action = {"selection": [M,H,W] mask | "bbox": int32 [M,4] | "point": int32 [M,2] | "bits": uint8 [M,128] bit-packed masks,
+        "operation": int32 [M]}; src_env int32 [M] = the env whose task (answer) row m belongs to (default: env m).  Returns (rows_out [M, L], reward int32 [M], terminated
         bool [M]).  Nothing of this env's own state is touched: expanding thousands of hypothetical states per launch is the point.
         in_place=True: `rows` (a tensor an earlier `transition` returned, or any view of a [M, 16-byte-multiple] buffer) is overwritten
         with the successor states — the kernel then rewrites only the planes the op changed, about half the time of the
@@ -564,6 +564,8 @@ class ARCVecEnv:
             form, pay = "bbox", action["bbox"].to(device=self.device, dtype=torch.int32).contiguous()
         elif "point" in action:
             form, pay = "point", action["point"].to(device=self.device, dtype=torch.int32).contiguous()
+        elif "bits" in action:
+            form, pay = "bits", action["bits"].to(device=self.device, dtype=torch.uint8).contiguous()
         else:
             form, pay = "mask", action["selection"].to(device=self.device, dtype=torch.int8).contiguous()
         op = action["operation"].to(device=self.device, dtype=torch.int32).contiguous()
@@ -579,8 +581,8 @@ class ARCVecEnv:
 
     def expand(self, rows, action, src_env=None):
         """K candidate actions per state row WITHOUT materialising the children — what a search does at every node.  rows int8 [M, L];
-        action = {"bbox": int32 [K,4] | "point": int32 [K,2], "operation": int32 [K]} (one action set for every row) or [M,K,..] /
-        [M,K] (a set per row); src_env as in `transition`.  Returns an Expansion of [M, K, ...] device tensors: reward, term, status
+        action = {"bbox": int32 [K,4] | "point": int32 [K,2] | "bits": uint8 [K,128] (bit-packed masks: `components(bits=True).bits`,
+        `search.pack_bits`), "operation": int32 [K]} (one action set for every row) or [M,K,..] / [M,K] (a set per row); src_env as in `transition`.  Returns an Expansion of [M, K, ...] device tensors: reward, term, status
         (ARCLE_ST_* bits of the child; such a child is its parent), hash int64 [M,K,2] = (state_hash, grid_hash) of the child state,
         dense int32 [M,K,2] = (correct, total) cells against the answer, parent_hash [M,2] — each equal to what `transition` + `hash_rows`
         give for that (row, action) pair.  This env's own state, status and counters are not touched."""
@@ -590,8 +592,10 @@ class ARCVecEnv:
             form, pay = "bbox", action["bbox"].to(device=self.device, dtype=torch.int32).contiguous()
         elif "point" in action:
             form, pay = "point", action["point"].to(device=self.device, dtype=torch.int32).contiguous()
+        elif "bits" in action:
+            form, pay = "bits", action["bits"].to(device=self.device, dtype=torch.uint8).contiguous()
         else:
-            raise ValueError("expand takes bbox or point actions")
+            raise ValueError("expand takes bbox, point or bits actions")
         op = action["operation"].to(device=self.device, dtype=torch.int32).contiguous()
         if src_env is not None:
             src_env = src_env.to(device=self.device, dtype=torch.int32).contiguous()

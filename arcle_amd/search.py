@@ -1,6 +1,7 @@
 """Search over ARCLE action sequences on top of `ARCVecEnv.expand`: the NumPy mirror of the device's state hash, a plain beam
 search, and the objects of a grid as candidate actions (`components_numpy`: the host mirror of arcle_components_rows;
-`object_actions` / `propose_objects`: its descriptors as a per-state action set for `beam_search(propose=...)`).
+`object_actions` / `propose_objects`: its descriptors as a per-state action set for `beam_search(propose=...)` — the objects'
+bounding boxes, or with masks=True their exact cells as bit rows; `pack_bits` / `unpack_bits`: that layout in torch).
 
 The hash is defined in include/arcle_hip.h (next to arcle_hash_rows) and computed on the device by arcle_amd/csrc/arcle_search.h;
 `hash_rows_numpy` restates it on the host — the same arrangement as arcle_amd/sampling.py for the device RNG — and is what the tests
@@ -13,6 +14,7 @@ import torch
 # enum arcle_plane ids of the planes a state row carries, in the row's (FlattenObservation) order, and the record byte every scalar
 # field of the row lands in (ARCLE_REC_*)
 _PLANE_ID = {"input": 0, "grid": 1, "selected": 2, "clip": 3, "object": 4, "object_sel": 5, "background": 6}
+BITS_STRIDE = 128  # bytes of a bit-packed selection mask (ARCLE_MAX_CELLS / 8)
 _REC_OFF = {"input_dim": 0, "grid_dim": 2, "clip_dim": 4, "object_dim": 6, "object_pos": 8, "trials_remain": 10, "terminated": 11,
             "active": 12, "rotation_parity": 13}
 
@@ -98,8 +100,8 @@ def beam_search(venv, rows, actions, width, depth, src_env=None, propose=None):
     """Beam search over sequences drawn from ONE candidate action set, scored by the dense pair (correct cells / total cells).
 
     venv: anything with `expand(rows, action, src_env)`, `transition(rows, action, src_env)` and `hash_rows(rows)` as ARCVecEnv has
-    them; rows int8 [M0, L] start states; actions = {"bbox": int32 [K,4] | "point": int32 [K,2], "operation": int32 [K]}; src_env
-    int32 [M0] = the env whose answer judges row m (default: env m).  Per depth: expand every frontier state by every action; drop
+    them; rows int8 [M0, L] start states; actions = {"bbox": int32 [K,4] | "point": int32 [K,2] | "bits": uint8 [K,128] (bit-packed
+    masks, `pack_bits`), "operation": int32 [K]}; src_env int32 [M0] = the env whose answer judges row m (default: env m).  Per depth: expand every frontier state by every action; drop
     children with a status bit and children whose state equals their parent's; drop states already seen (in an earlier depth, or
     twice in this one: the lowest child index stays); if a child's grid IS the answer (correct == total: exactly when a Submit
     would pay — with unequal dims the total exceeds the common rectangle — so the candidate set needs no Submit) return the action
@@ -109,20 +111,25 @@ def beam_search(venv, rows, actions, width, depth, src_env=None, propose=None):
     propose: a callable `propose(venv, frontier_rows) -> {"bbox": int32 [M, K, 4], "operation": int32 [M, K]}` called at every
     depth for a candidate set PER STATE (`propose_objects`: the connected components of each state's grid); `actions` may then be
     None, and BeamResult.sequence is the list of the 5-tuples (x1, y1, x2, y2, op) themselves — BBoxWrapper actions; an index into
-    a per-state set names nothing.  Slots with operation -1 are padding: their children carry a status bit and are dropped."""
+    a per-state set names nothing.  Slots with operation -1 are padding: their children carry a status bit and are dropped.
+    A propose that returns {"bits": uint8 [M, K, 128], "operation": ...} (`propose_objects(masks=True)`: each object's exact cells)
+    makes the sequence a list of (selection, op), selection a bool NumPy array [H, W] (H, W = venv.H, venv.W): what the reference's
+    `step({"selection": selection, "operation": op})` takes."""
     dev = rows.device
+
+    def payload_of(a):
+        form = "bbox" if "bbox" in a else "point" if "point" in a else "bits"
+        return form, a[form].to(device=dev, dtype=torch.uint8 if form == "bits" else torch.int32).contiguous()
     if propose is None:
-        form = "bbox" if "bbox" in actions else "point"
-        pay = actions[form].to(device=dev, dtype=torch.int32).contiguous()
+        form, pay = payload_of(actions)
         op = actions["operation"].to(device=dev, dtype=torch.int32).contiguous()
         assert pay.dim() == 2 and op.dim() == 1, "beam_search takes one candidate set for every state"
         K = int(op.shape[0])
-    else:
-        form = "bbox"
     M0 = int(rows.shape[0])
     src = (torch.arange(M0, device=dev) if src_env is None else src_env.to(dev)).to(torch.int32)
     root = torch.arange(M0, device=dev)
-    path = torch.empty((M0, 0), dtype=torch.int64, device=dev) if propose is None else torch.empty((M0, 0, 5), dtype=torch.int32, device=dev)
+    # the actions behind every frontier state: indices into the one set, or (propose) the payloads and ops themselves, [M, depth, ...]
+    path, path_op = (torch.empty((M0, 0), dtype=torch.int64, device=dev), None) if propose is None else (None, torch.empty((M0, 0), dtype=torch.int32, device=dev))
     seen = venv.hash_rows(rows)[:, 0].clone()
     frontier, counts = rows, []
     for _ in range(depth):
@@ -131,10 +138,13 @@ def beam_search(venv, rows, actions, width, depth, src_env=None, propose=None):
             break
         if propose is not None:
             cand = propose(venv, frontier)
-            pay = cand["bbox"].to(device=dev, dtype=torch.int32).contiguous()
+            form, pay = payload_of(cand)
+            assert form != "point", "propose returns bbox or bits candidates"
             op = cand["operation"].to(device=dev, dtype=torch.int32).contiguous()
             assert pay.dim() == 3 and op.dim() == 2 and pay.shape[0] == M, "propose returns a candidate set per frontier row"
             K = int(op.shape[1])
+            if path is None:  # (shaped by the first candidate set: 4 int32 of a box, or the bytes of a bit row)
+                path = torch.empty((M0, 0, pay.shape[2]), dtype=pay.dtype, device=dev)
         ex = venv.expand(frontier, {form: pay, "operation": op}, src)
         h = ex.hash[:, :, 0]
         ok = (ex.status == 0) & (h != ex.parent_hash[:, :1])
@@ -155,8 +165,8 @@ def beam_search(venv, rows, actions, width, depth, src_env=None, propose=None):
         if propose is None:
             step_pay, step_op, step = pay.index_select(0, k), op.index_select(0, k), k.reshape(-1, 1)
         else:  # the survivors' actions, gathered from their parents' sets
-            step_pay, step_op = pay.reshape(-1, 4).index_select(0, idx), op.reshape(-1).index_select(0, idx)
-            step = torch.cat([step_pay, step_op.reshape(-1, 1)], 1).reshape(-1, 1, 5)
+            step_pay, step_op = pay.reshape(-1, pay.shape[2]).index_select(0, idx), op.reshape(-1).index_select(0, idx)
+            step = step_pay.unsqueeze(1)
         goal = (c == t) & (t > 0)
         if bool(goal.any()):
             g = int(torch.nonzero(goal)[0])
@@ -164,7 +174,11 @@ def beam_search(venv, rows, actions, width, depth, src_env=None, propose=None):
             if propose is None:
                 seq = path[parent[g]].tolist() + [int(k[g])]
             else:
-                seq = [tuple(a) for a in torch.cat([path[parent[g]], step[g]], 0).tolist()]
+                sels, ops = torch.cat([path[parent[g]], step[g]], 0), torch.cat([path_op[parent[g]], step_op[g:g + 1]], 0).tolist()
+                if form == "bbox":
+                    seq = [tuple(a) + (o,) for a, o in zip(sels.tolist(), ops)]
+                else:
+                    seq = list(zip(unpack_bits(sels, venv.H, venv.W).cpu().numpy(), ops))
             return BeamResult(seq, counts, int(root[parent[g]]))
         # correct / total as an integer key: floor(c * 2^32 / t).  Two different fractions with totals below 2^16 differ by at least
         # 1 / (t1 * t2) > 2^-32, so their keys differ in the same direction; equal fractions give equal keys
@@ -179,6 +193,8 @@ def beam_search(venv, rows, actions, width, depth, src_env=None, propose=None):
         frontier, _, _ = venv.transition(frontier.index_select(0, parent), {form: step_pay.index_select(0, best), "operation": step_op.index_select(0, best)},
                                          src_next)
         path = torch.cat([path.index_select(0, parent), step.index_select(0, best)], 1)
+        if propose is not None:
+            path_op = torch.cat([path_op.index_select(0, parent), step_op.index_select(0, best).reshape(-1, 1)], 1)
         root, src = root.index_select(0, parent), src_next
     return BeamResult(None, counts, None)
 
@@ -220,13 +236,35 @@ def components_numpy(grid, grid_dim, max_components, skip_color=-1):
     return n, int(todo.sum()), comp, masks
 
 
-def object_actions(comp, box_ops, seed_ops):
+def pack_bits(masks):
+    """Selection masks [..., H, W] (bool, or int8: truthy = non-zero) -> uint8 [..., 128] bit rows on the masks' device: bit f & 7 of
+    byte f >> 3 is cell f = row * W + col — the layout of `step_bits`, `components(bits=True)` and the "bits" form of `expand` /
+    `transition`.  (arcle_pack_mask_bits does the same for exactly the handle's N envs; a search packs M * K masks.)"""
+    lead, P = tuple(masks.shape[:-2]), int(masks.shape[-2]) * int(masks.shape[-1])
+    assert P <= 8 * BITS_STRIDE, "pack_bits: grids of at most 1024 cells"
+    flat = torch.zeros(lead + (8 * BITS_STRIDE,), dtype=torch.uint8, device=masks.device)
+    flat[..., :P] = (masks != 0).reshape(lead + (P,))
+    w = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.uint8, device=masks.device)
+    return (flat.reshape(lead + (BITS_STRIDE, 8)) * w).sum(-1, dtype=torch.uint8)  # (eight distinct bits: the byte sum cannot carry)
+
+
+def unpack_bits(bits, H, W):
+    """The inverse of pack_bits: uint8 [..., 128] bit rows -> bool [..., H, W] (bits at cell indices >= H * W are dropped)."""
+    sh = torch.arange(8, dtype=torch.int32, device=bits.device)
+    cells = ((bits.to(torch.int32).unsqueeze(-1) >> sh) & 1).reshape(tuple(bits.shape[:-1]) + (-1,))
+    return cells[..., :H * W].reshape(tuple(bits.shape[:-1]) + (H, W)).to(torch.bool)
+
+
+def object_actions(comp, box_ops, seed_ops, masks=False):
     """The components of M states (`ARCVecEnv.components`: count [M], box [M, C, 4], seed [M, C, 2]) as a candidate set per state:
     {"bbox": int32 [M, K, 4], "operation": int32 [M, K]}, K = C * (len(box_ops) + len(seed_ops)).  Component k contributes its box
     with every op of box_ops (Move / Rotate / Flip / Copy want the box of a shape), then its seed as the 1 x 1 box (sx, sy, sx, sy)
     with every op of seed_ops (a 1 x 1 rectangle is what FloodFill accepts).  The slots of components k >= count get operation -1:
     expansion reports ARCLE_ST_BAD_OP for such a child alone, and beam_search drops children with a status bit.  Pure indexing on the
-    device: no host synchronisation."""
+    device: no host synchronisation.
+    masks=True (needs comp.bits, `components(bits=True)`): {"bits": uint8 [M, K, 128], "operation": int32 [M, K]} — component k's
+    exact cells with every op of box_ops (a box selects whatever else lies inside it), then the one-bit mask of its seed with every
+    op of seed_ops (FloodFill acts only on a selection of one cell); the slots of components k >= count get a zero mask."""
     box, seed, count = comp.box, comp.seed, comp.count
     M, C = int(box.shape[0]), int(box.shape[1])
     dev = box.device
@@ -236,15 +274,28 @@ def object_actions(comp, box_ops, seed_ops):
     bb = torch.cat([box.reshape(M, C, 1, 4).expand(M, C, nb, 4), torch.cat([seed, seed], 2).reshape(M, C, 1, 4).expand(M, C, ns, 4)], 2)
     there = (torch.arange(C, device=dev).reshape(1, C) < count.reshape(M, 1)).reshape(M, C, 1)
     op = torch.where(there, ops.reshape(1, 1, per), torch.full((), -1, dtype=torch.int32, device=dev))
+    if masks:
+        assert comp.bits is not None, "object_actions(masks=True) needs the components' bit masks (components(bits=True))"
+        cells = torch.where(there, comp.bits, torch.zeros((), dtype=torch.uint8, device=dev))  # (entries >= count were never written)
+        # the seed is the component's first cell in row-major order: the lowest set bit of its row
+        first = (cells != 0).to(torch.uint8).argmax(-1, keepdim=True)
+        v = cells.gather(-1, first).to(torch.int32)
+        one = torch.zeros_like(cells).scatter_(-1, first, (v & -v).to(torch.uint8))
+        S_ = int(cells.shape[-1])
+        mb = torch.cat([cells.reshape(M, C, 1, S_).expand(M, C, nb, S_), one.reshape(M, C, 1, S_).expand(M, C, ns, S_)], 2)
+        return {"bits": mb.reshape(M, C * per, S_).contiguous(), "operation": op.reshape(M, C * per).to(torch.int32).contiguous()}
     bb = torch.where(there.reshape(M, C, 1, 1), bb.to(torch.int32), torch.zeros((), dtype=torch.int32, device=dev))  # (entries >= count were never written)
     return {"bbox": bb.reshape(M, C * per, 4).contiguous(), "operation": op.reshape(M, C * per).to(torch.int32).contiguous()}
 
 
-def propose_objects(box_ops, seed_ops, max_components=16, skip_color=0):
+def propose_objects(box_ops, seed_ops, max_components=16, skip_color=0, masks=False):
     """A `propose` for beam_search: at every depth the connected components of each frontier state's grid (`venv.components`, one
-    launch) with box_ops on their boxes and seed_ops on their seeds (`object_actions`)."""
+    launch) with box_ops on their boxes and seed_ops on their seeds (`object_actions`); masks=True: on their exact cells, as bit
+    rows, instead of their boxes."""
     box_ops, seed_ops = list(box_ops), list(seed_ops)
 
     def propose(venv, rows):
-        return object_actions(venv.components(rows, max_components=max_components, skip_color=skip_color), box_ops, seed_ops)
+        comp = venv.components(rows, max_components=max_components, skip_color=skip_color, bits=True) if masks else \
+            venv.components(rows, max_components=max_components, skip_color=skip_color)
+        return object_actions(comp, box_ops, seed_ops, masks)
     return propose

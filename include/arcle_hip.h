@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ARCLE_ABI_VERSION 8
+#define ARCLE_ABI_VERSION 9
 #define ARCLE_MAX_OPS 64
 #define ARCLE_MAX_CELLS 1024 /* H*W <= 1024: one 64-lane wavefront x 16 cells holds a plane (the one-wavefront-per-env kernels);
                                 larger planes (H, W <= 127) are served by the workgroup-per-env kernels — see "Grids beyond
@@ -438,9 +438,12 @@ int arcle_set_flat_seq(arcle_env* env, int32_t seq);
  *                          -> row r of rows_out; the handle's resident envs are not touched, so any number of hypothetical states
  *                          (planning / search) can be expanded per launch.  Submit and the reward compare with the answer of resident
  *                          env src_env[r] (device int32[n_rows]; NULL = env r, then n_rows <= n_envs).  ingress: ARCLE_INGRESS_MASK /
- *                          _BBOX / _POINT with the matching `sel` array [n_rows][...]; op int32[n_rows]; reward int32[n_rows],
+ *                          _BBOX / _POINT / _BITS with the matching `sel` array [n_rows][...] (_BITS: uint8 [n_rows][128] as for
+ *                          arcle_step_bits, 2-byte aligned; handles of at most ARCLE_MAX_CELLS cells per plane only — on a larger
+ *                          grid the form is refused with ARCLE_ERR_ARG before any allocation or launch); op int32[n_rows]; reward int32[n_rows],
  *                          term uint8[n_rows] out; tail as arcle_set_flat_output_ex (action_steps = 1, submit_count = 1 iff the
- *                          Submit counted, base.py:174-175).  flags: ARCLE_STEP_RESET_ON_SUBMIT | _DENSE | _CONTINUE_RULE.
+ *                          Submit counted, base.py:174-175).  flags: ARCLE_STEP_RESET_ON_SUBMIT | _DENSE | _CONTINUE_RULE
+ *                          (the rule compares cells: _MASK or _BITS selections, ARCLE_ERR_CONFIG with tuples).
  *                          rows_out may equal rows_in when the strides agree: IN PLACE, only the planes the op changed (and the scalars)
  *                          are rewritten — about half the time of the out-of-place form. */
 int arcle_get_state_rows(arcle_env* env, int8_t* rows, int32_t stride, void* stream);
@@ -466,9 +469,12 @@ int arcle_transition_rows(arcle_env* env, int32_t n_rows, const int8_t* rows_in,
  * arcle_amd/search.py::hash_rows_numpy is the same formula in NumPy.  One wavefront per row, any row alignment, stride >= the row length.
  *
  * arcle_expand_rows: K = n_actions candidate actions per state row, nothing but verdicts written.  rows [n_rows] are read only.
- * Actions: ARCLE_INGRESS_BBOX (sel int32 [..][4]) or ARCLE_INGRESS_POINT (int32 [..][2]) with op int32 [..]; action_row_stride = 0:
- * ONE set of K actions applied to every row ([K] arrays), = n_actions: a set per row ([n_rows][K]).  Mask ingress is not served
- * here (ARCLE_ERR_ARG).  Outputs, all [n_rows][K], child c = m * K + k: reward int32, term uint8, status uint8 (the ARCLE_ST_* bits
+ * Actions: ARCLE_INGRESS_BBOX (sel int32 [..][4]), ARCLE_INGRESS_POINT (int32 [..][2]) or ARCLE_INGRESS_BITS (uint8 [..][S], S =
+ * arcle_mask_bits_stride(): bit-packed boolean masks in the layout of arcle_step_bits, 2-byte aligned — ARCLE_ERR_ARG otherwise; bits
+ * at cell indices >= H*W are ignored) with op int32 [..]; action_row_stride = 0: ONE set of K actions applied to every row ([K]
+ * arrays), = n_actions: a set per row ([n_rows][K]).  The `bits` array arcle_components_rows writes when called with max_comp == K is
+ * a valid per-row `sel` as it stands (zero-filled by the caller: entries of components that do not exist are not written; give their
+ * slots an out-of-range op).  Int8 masks (ARCLE_INGRESS_MASK) and ARCLE_INGRESS_BBOX5 are not served here (ARCLE_ERR_ARG).  Outputs, all [n_rows][K], child c = m * K + k: reward int32, term uint8, status uint8 (the ARCLE_ST_* bits
  * child c raised), hash uint64 [..][2], optional dense int32 [..][2] (non-NULL implies ARCLE_STEP_DENSE: correct cells, total cells
  * of the child's grid against the answer of env src_env[m]), optional parent_hash uint64 [n_rows][2].  flags: ARCLE_STEP_RESET_ON_SUBMIT
  * | _DENSE.  For every (m, k) the outputs equal what arcle_transition_rows reports for (row m, action (m, k), src_env[m], same flags)
