@@ -2,9 +2,11 @@
 oracle/stubs) — build-container only, test infrastructure only.
 
 Used by oracle/diff_vs_reference.py (differential fuzz of oracle/arcle_oracle.c against the
-reference) and tests/golden/make_golden.py (captures the committed golden vectors).  Nothing
-here is importable on the GPU box (no /root/reference there) and nothing in arcle_amd/, bench.py
-or the gpu tests imports it.
+reference) and tests/golden/make_golden.py (captures the committed golden vectors).  Whatever
+imports the reference works in the build container only (there is no reference on the GPU box);
+nothing in arcle_amd/ or bench.py imports this module.  `variant_table` alone — descriptor tables
+built from oracle.py, no reference import — is also used by the tests, gpu tests included
+(tests/test_hip_parity.py, tests/test_big_hip.py, tests/deepstate.py).
 """
 import os
 import sys

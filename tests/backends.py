@@ -973,13 +973,15 @@ def random_payload(rng, ing, N, H, W, int8_masks=False, bad_tuples=False):
 
 
 def random_trace_compare(backend_cls, kind, ops, H, W, N, S, seed, max_trial=-1, flags=0, op_weights=None,
-                         bad_ops=False, new_forms=False, int8_masks=False):
+                         bad_ops=False, new_forms=False, int8_masks=False, observer=None):
     """Steps `backend_cls` and the oracle side by side on seeded random tasks/actions; returns mismatches.
     new_forms: the backend under test receives bbox actions as 5-tuple records (bbox5) and masks bit-packed (bits; the masks are
     boolean then) — the oracle gets the classic forms of the same actions.
     int8_masks: every action is a full mask of arbitrary int8 values (out of the Gym contract, but NumPy takes them: sel > 0 / != 0 / sum /
     argmax differ then): sparse values in [-3, 3], one cell of 1 / 2 / -1 / 127 / -128, the pair {2, -1} (sum 1, arg-max at the 2), 0 / 1
-    noise with a few negatives, a block of ones holding one 5."""
+    noise with a few negatives, a block of ones holding one 5.
+    observer: an object told about every oracle step — before(orc) just before it, after(orc, ingress, payload, op, flags, reward) just
+    after it (tests/deepstate.py counts the situations the stream reaches that way); it must leave the oracle as it is."""
     rng = np.random.default_rng(seed)
     be = backend_cls(N, H, W, max_trial, kind, ops)
     orc = OracleBackend(N, H, W, max_trial, kind, ops)
@@ -1022,7 +1024,11 @@ def random_trace_compare(backend_cls, kind, ops, H, W, N, S, seed, max_trial=-1,
             r1, t1 = be.step("bits", pack_bits(pay), op, flags)
         else:
             r1, t1 = be.step(ing, pay, op, flags)
+        if observer is not None:
+            observer.before(orc)
         r2, t2 = orc.step(ing, pay, op, flags)
+        if observer is not None:
+            observer.after(orc, ing, pay, op, flags, r2)
         tag = f"{kind} {H}x{W} seed {seed} step {s} ingress {ing}{' (new form)' if new_forms else ''}"
         if not np.array_equal(r1, r2):
             errs.append(f"{tag}: reward mismatch envs {np.nonzero(r1 != r2)[0].tolist()}")
