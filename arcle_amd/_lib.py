@@ -16,7 +16,7 @@ UNITS = [os.path.join(_CSRC, "arcle_hip.hip"), os.path.join(_CSRC, "arcle_big.hi
 SOURCES = UNITS + [os.path.join(_CSRC, "arcle_wave.h"), os.path.join(_CSRC, "arcle_group.h"), os.path.join(_CSRC, "arcle_search.h"), os.path.join(_CSRC, "arcle_components.h"), os.path.join(_CSRC, "arcle_big.h"), os.path.join(_CSRC, "arcle_big_params.h"),
                    os.path.join(_CSRC, "..", "..", "include", "arcle_hip.h")]
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 N_PLANES = 8
 MAX_OPS = 64
 BITS_STRIDE = 128  # bytes between envs of a bit-packed mask array (ARCLE_MAX_CELLS / 8)
@@ -28,7 +28,7 @@ EXPORTS = ["arcle_abi_version", "arcle_create", "arcle_destroy", "arcle_get_buff
            "arcle_packed_obs_size", "arcle_pack_obs", "arcle_set_packed_output", "arcle_set_sampler", "arcle_reset_sampled",
            "arcle_reset_from_table_aug", "arcle_set_dense_output", "arcle_invalidate", "arcle_flat_obs_size", "arcle_flatten_obs",
            "arcle_set_flat_output", "arcle_set_flat_output_ex", "arcle_set_flat_seq", "arcle_get_state_rows", "arcle_set_state_rows",
-           "arcle_transition_rows", "arcle_hash_rows", "arcle_expand_rows", "arcle_components_rows", "arcle_get_plane", "arcle_set_plane", "arcle_get_status",
+           "arcle_transition_rows", "arcle_hash_rows", "arcle_expand_rows", "arcle_expand_macros", "arcle_components_rows", "arcle_get_plane", "arcle_set_plane", "arcle_get_status",
            "arcle_enable_accounting", "arcle_get_accounting", "arcle_get_accounting_ex", "arcle_last_error"]
 
 
@@ -132,6 +132,7 @@ def load(path, abi_version=None):
     L.arcle_transition_rows.argtypes = [vp, i32, vp, i32, ctypes.c_int, vp, vp, vp, vp, i32, ctypes.c_int, vp, vp, u32, vp]
     L.arcle_hash_rows.argtypes = [vp, i32, vp, i32, vp, vp]
     L.arcle_expand_rows.argtypes = [vp, i32, vp, i32, i32, ctypes.c_int, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, u32, vp]
+    L.arcle_expand_macros.argtypes = [vp, i32, vp, i32, i32, i32, ctypes.c_int, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, u32, vp]
     L.arcle_components_rows.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp]
     L.arcle_get_plane.argtypes = [vp, ctypes.c_int, vp, vp]
     L.arcle_set_plane.argtypes = [vp, ctypes.c_int, vp, vp]

@@ -485,6 +485,19 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) __attribute__((amdgpu_waves_per_
   arcle::wave_expand_row<ING, FW>(x, &lds.wave[threadIdx.x >> 6], lds.lut, (int)m, k0, k1, (int)(threadIdx.x & 63));
 }
 
+// the same split for macros (arcle_expand_macros): wave v runs macros [j * chunk, (j + 1) * chunk) of parent row m, each up to max_len steps
+template <int ING, int FW>
+__global__ __launch_bounds__(64 * WAVES_PER_WG) __attribute__((amdgpu_waves_per_eu(ARCLE_EXPAND_WAVES_PER_EU))) void arcle_expand_macros_kernel(const arcle::MacroParams y) {
+  __shared__ BlockLDS lds;
+  arcle::lut_init(lds.lut, (int)threadIdx.x);
+  xl::wg_barrier();
+  const uint32_t v = (uint32_t)wave_of_launch();
+  if (v >= (uint32_t)y.x.p.n_envs * (uint32_t)y.x.n_chunks) return;
+  const uint32_t m = v / (uint32_t)y.x.n_chunks, j = v - m * (uint32_t)y.x.n_chunks;
+  const int k0 = (int)j * y.x.chunk, k1 = k0 + y.x.chunk < y.x.n_actions ? k0 + y.x.chunk : y.x.n_actions;
+  arcle::wave_expand_macros_row<ING, FW>(y, &lds.wave[threadIdx.x >> 6], lds.lut, (int)m, k0, k1, (int)(threadIdx.x & 63));
+}
+
 // one wavefront per row, 4-wave workgroups; no LDS (the kernel neither stages a plane nor expands a mask: no table, no tile)
 static constexpr int COMP_WAVES_PER_WG = 4;
 template <int FW>
@@ -765,9 +778,11 @@ extern "C" int arcle_create(const arcle_config* cfg, const arcle_buffers* bufs, 
     }
   } else {
     e->owns_bufs = true;
+    // (ARCLE_PLANE_SLACK bytes behind every plane: the row kernels request the answer plane from all 64 lanes, 1024 bytes from the
+    // env's plane on whatever the plane stride — for the last envs of a handle with a stride below 1024 that is behind the plane)
     for (int i = 0; i < ARCLE_N_PLANES; i++) {
-      if (hipMalloc((void**)&e->bufs.plane[i], plane_bytes) != hipSuccess ||
-          hipMemset(e->bufs.plane[i], 0, plane_bytes) != hipSuccess) {
+      if (hipMalloc((void**)&e->bufs.plane[i], plane_bytes + ARCLE_PLANE_SLACK) != hipSuccess ||
+          hipMemset(e->bufs.plane[i], 0, plane_bytes + ARCLE_PLANE_SLACK) != hipSuccess) {
         arcle_destroy(e);
         return ARCLE_ERR_HIP;
       }
@@ -2076,6 +2091,61 @@ extern "C" int arcle_expand_rows(arcle_env* e, int32_t n_rows, const int8_t* row
   const dim3 g = grid_for(n_rows * x.n_chunks), b(64 * WAVES_PER_WG);
   with_form<EXPAND_FORMS, false>(ingress, width_class(e->base), [&](auto ing, auto fw) {
     hipLaunchKernelGGL((arcle_expand_kernel<decltype(ing)::value, decltype(fw)::value>), g, b, 0, (hipStream_t)stream, x);
+    return ARCLE_OK;
+  });
+  HIP_TRY(e, hipGetLastError());
+  return ARCLE_OK;
+}
+
+// K macros — sequences of up to max_len steps — per row: arcle_expand_rows with the step loop inside the wave.  The chunk rule counts
+// macros, as it counts actions there (the wave's set-up is the same; its work per candidate is max_len times as long at most).
+extern "C" int arcle_expand_macros(arcle_env* e, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t n_actions, int32_t max_len,
+                                   int ingress, const void* sel, const int32_t* op, const int32_t* len, int32_t action_row_stride,
+                                   const int32_t* src_env, int32_t* reward, uint8_t* term, uint8_t* status, uint64_t* hash, int32_t* dense,
+                                   uint64_t* parent_hash, uint32_t flags, void* stream) {
+  if (!e || !sel || !op || !reward || !term || !status || !hash) return ARCLE_ERR_ARG;
+  if (n_rows <= 0 || n_actions <= 0) return fail(e, ARCLE_ERR_ARG, "n_rows and n_actions must be positive");
+  if (max_len < 1) return fail(e, ARCLE_ERR_ARG, "arcle_expand_macros: max_len must be at least 1");
+  if (action_row_stride != 0 && action_row_stride != n_actions)
+    return fail(e, ARCLE_ERR_ARG, "action_row_stride: 0 (one macro set for every row) or n_actions (a set per row)");
+  if (!takes(EXPAND_FORMS, ingress)) return fail(e, ARCLE_ERR_ARG, "arcle_expand_macros takes bbox, point or bit-row selections");
+  if (ingress == arcle::INGRESS_BITS)
+    if (int rc = need_bits_aligned(e, sel)) return rc;
+  if (e->big) return fail(e, ARCLE_ERR_CONFIG, "arcle_expand_macros: handles of at most 1024 cells per plane (ARCLE_MAX_CELLS)");
+  if (int rc = need_src_env(e, n_rows, src_env)) return rc;
+  if ((int64_t)n_rows * n_actions * max_len >= (1ll << 28)) return fail(e, ARCLE_ERR_ARG, "too many steps (n_rows * n_actions * max_len < 2^28)");
+  if (int rc = need_op_table(e)) return rc;
+  if (dense) flags |= ARCLE_STEP_DENSE;
+  if (flags & ~(ARCLE_STEP_RESET_ON_SUBMIT | ARCLE_STEP_DENSE)) return fail(e, ARCLE_ERR_ARG, "arcle_expand_macros takes ARCLE_STEP_RESET_ON_SUBMIT / _DENSE only");
+  if ((flags & ARCLE_STEP_DENSE) && !dense) return fail(e, ARCLE_ERR_ARG, "ARCLE_STEP_DENSE without a dense output array");
+  if ((flags & ARCLE_STEP_DENSE) && !e->bufs.plane[ARCLE_PL_ANSWER]) return fail(e, ARCLE_ERR_CONFIG, "ARCLE_STEP_DENSE needs the answer plane");
+  if (int rc = check_rows(e, rows, stride, 0)) return rc;
+  DeviceGuard guard(e->device);
+  arcle::MacroParams y = {};
+  arcle::ExpandParams& x = y.x;
+  StepCall c = action_call(ingress, sel, op, reward, term, flags);
+  c.dense = dense;
+  StepParams& p = x.p;
+  p = make_params(e, c);
+  p.n_resident = p.n_envs;
+  p.n_envs = n_rows;
+  p.task_idx = src_env;
+  p.rows_in = rows;
+  p.rows_in_stride = stride;
+  p.dense_cache = nullptr;
+  p.status = e->d_status + 2;  // speculation, as arcle_expand_rows: the handle's sticky word stays as it is
+  x.n_actions = n_actions;
+  x.action_row_stride = action_row_stride;
+  x.chunk = expand_chunk(n_rows, n_actions);
+  x.n_chunks = (n_actions + x.chunk - 1) / x.chunk;
+  x.status_out = status;
+  x.hash = hash;
+  x.parent_hash = parent_hash;
+  y.max_len = max_len;
+  y.len = len;
+  const dim3 g = grid_for(n_rows * x.n_chunks), b(64 * WAVES_PER_WG);
+  with_form<EXPAND_FORMS, false>(ingress, width_class(e->base), [&](auto ing, auto fw) {
+    hipLaunchKernelGGL((arcle_expand_macros_kernel<decltype(ing)::value, decltype(fw)::value>), g, b, 0, (hipStream_t)stream, y);
     return ARCLE_OK;
   });
   HIP_TRY(e, hipGetLastError());

@@ -257,4 +257,137 @@ ARCLE_DEV void wave_expand_row(const ExpandParams& x, WaveLDS* lds, const U2* lu
   }
 }
 
+// launch parameters of arcle_expand_macros: the expansion's (sel / op are [..][K][T][..], every output still [M][K]) and what a macro
+// adds.  A struct of its own: ExpandParams is an argument of the kernels above and stays as it is.
+struct MacroParams {
+  ExpandParams x;
+  int32_t max_len;     // T: steps a macro has room for
+  const int32_t* len;  // int32 [..][K]: steps macro (m, k) runs, 1 .. T; NULL: every macro runs T
+};
+
+// arcle_expand_macros: parent row m, macros [k0, k1) of its set.  The wave's set-up is wave_expand_row's (restated, not shared: that
+// body's code object is pinned, profiles/expand_macros_codeobj.txt).  Per macro: record and planes back to the parent, then len steps of
+// step_core on the SAME working copy — step t + 1 sees what step t left in w.cache, as the rollout kernel chains its steps — and one
+// set of verdicts: the rewards' sum, the last step's terminated, the OR of the status bits, the dense pair the last step wrote, and
+// the hash of the final state.  `stored` and `dirty` are per step (step_core reads `stored` for the dense pair; the in-place
+// arcle_transition_rows this kernel stands for starts every call with them clear); the hash needs every plane ANY step stored,
+// which `touched` collects.  A macro whose len is outside [1, T] runs no step: ARCLE_ST_BAD_OP, the child is the parent.
+template <int ING, int FW>
+ARCLE_DEV void wave_expand_macros_row(const MacroParams& y, WaveLDS* lds, const U2* lut, int m, int k0, int k1, int lane) {
+  const ExpandParams& x = y.x;
+  const StepParams& p = x.p;
+  Wave w(p, lds, lut, lane, ING, FW, false);
+  int src = m;
+  if (p.task_idx) src = (int)xl::uniform((uint32_t)p.task_idx[m]);
+  uint32_t st0 = 0;
+  if (src < 0 || src >= p.n_resident) {  // no such env to take the answer from: every child is the parent, with the status bit
+    st0 = ARCLE_ST_BAD_TASK;
+    src = 0;
+  }
+  const int8_t* rin = p.rows_in + (size_t)m * p.rows_in_stride;
+  w.set_env(src);
+  Rec r0 = load_rec(p, src);  // (answer_dim; every state field is overwritten from the row)
+  read_state_row(w, rin, r0, [&](int, const U4&) {}, false);
+  w.resident = true;
+  w.row_src = rin;
+  w.answer_env = src;
+  const HashKeys hk = hash_keys(w);
+  Hash2 pt[ARCLE_N_PLANES - 1];
+  Hash2 pall = {0u, 0u};
+#if ARCLE_EXPAND_KEEP_PARENT
+  U4 par[ARCLE_N_PLANES - 1];
+  uint32_t par_have = 0;
+#endif
+#pragma unroll
+  for (int pl = 0; pl < ARCLE_N_PLANES - 1; pl++) {
+    pt[pl] = Hash2{0u, 0u};
+    if (p.plane[pl]) {
+      const U4 v = row_plane(w, rin, row_offset(p, pl));
+#if ARCLE_EXPAND_KEEP_PARENT
+      par[pl] = v;
+      par_have |= 1u << pl;
+#endif
+      pt[pl] = hash_plane_lane(hk, pl, v);
+      pall.a += pt[pl].a;
+      pall.b += pt[pl].b;
+    }
+  }
+  // (the answer plane through the lanes that own bytes of it: see wave_expand_row)
+  U4 ans = u4_zero();
+  if (p.plane[ARCLE_PL_ANSWER] && 16 * lane < p.PS) ans = xl::load16(p.plane[ARCLE_PL_ANSWER], (uint32_t)src * (uint32_t)p.PS + 16u * (uint32_t)lane);
+  if (x.parent_hash && k0 == 0) hash_finish(w, r0, pall, pt[ARCLE_PL_GRID], x.parent_hash + 2 * (size_t)m);
+  const size_t a0 = (size_t)m * (size_t)x.action_row_stride;  // first macro of this row's set
+  const int T = y.max_len;
+  // step t of macro a is entry a * T + t of sel / op; the next step's tuple and op — of this macro, or the first of the next — are
+  // requested under the current op
+  U4 pay = load_payload(w, (int)((a0 + (size_t)k0) * (size_t)T), 0, p.sel);
+  int op = (int)xl::uniform((uint32_t)p.op[(a0 + (size_t)k0) * (size_t)T]);
+  int len = y.len ? (int)xl::uniform((uint32_t)y.len[a0 + (size_t)k0]) : T;
+  for (int k = k0; k < k1; k++) {
+    const int kn = k + 1 < k1 ? k + 1 : k;
+    const size_t first_next = (a0 + (size_t)kn) * (size_t)T;
+    const int len_next = y.len ? (int)xl::uniform((uint32_t)y.len[a0 + (size_t)kn]) : T;
+    const int c = m * x.n_actions + k;  // child index: every output is [M][K]
+    Rec r = r0;
+#if ARCLE_EXPAND_KEEP_PARENT
+#pragma unroll
+    for (int pl = 0; pl < ARCLE_N_PLANES - 1; pl++)
+      if (p.plane[pl]) w.cache[pl] = par[pl];
+    w.have = par_have;
+#else
+    w.have = 0;
+#endif
+    w.cache[ARCLE_PL_ANSWER] = ans;
+    w.have |= 1u << ARCLE_PL_ANSWER;
+    w.env = c;
+    uint32_t status = st0, touched = 0;
+    if ((uint32_t)(len - 1) >= (uint32_t)T) status |= ARCLE_ST_BAD_OP;
+    const int n = status ? 0 : len;
+    int reward = 0;
+    bool term = false;
+    const size_t first = (a0 + (size_t)k) * (size_t)T;
+#pragma nounroll
+    for (int t = 0; t < n; t++) {
+      const size_t nx = t + 1 < n ? first + (size_t)t + 1 : first_next;
+      const U4 pay_next = load_payload(w, (int)nx, 0, p.sel);
+      const int op_next = (int)xl::uniform((uint32_t)p.op[nx]);
+      I2 cnt;
+      cnt.x = cnt.y = 0;
+      w.dirty = 0;
+      w.stored = 0;
+      const StepOut out = step_core<ING, FW, 0, 1>(w, r, cnt, pay, op);
+      xl::lanes_converged();
+      touched |= w.stored;
+      status |= out.status;
+      reward += out.reward;
+      term = out.term;
+      pay = pay_next;
+      op = op_next;
+    }
+    if (n == 0) {  // the child that did not happen: the next macro's first step was not requested under a step
+      if (p.flags & ARCLE_STEP_DENSE) dense_none(w);
+      pay = load_payload(w, (int)first_next, 0, p.sel);
+      op = (int)xl::uniform((uint32_t)p.op[first_next]);
+    }
+    // child terms: the parent's, with the share of every plane some step stored replaced
+    Hash2 all = pall, grid = pt[ARCLE_PL_GRID];
+#pragma unroll
+    for (int pl = 0; pl < ARCLE_N_PLANES - 1; pl++) {
+      if (p.plane[pl] && (touched & (1u << pl))) {
+        const Hash2 t = hash_plane_lane(hk, pl, w.cache[pl]);
+        all.a += t.a - pt[pl].a;
+        all.b += t.b - pt[pl].b;
+        if (pl == ARCLE_PL_GRID) grid = t;
+      }
+    }
+    hash_finish(w, r, all, grid, x.hash + 2 * (size_t)c);
+    if (lane == 0) {
+      p.reward[c] = reward;
+      p.term[c] = (uint8_t)term;
+      x.status_out[c] = (uint8_t)(status & 0xffu);
+    }
+    len = len_next;
+  }
+}
+
 }  // namespace arcle

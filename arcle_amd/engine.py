@@ -87,6 +87,7 @@ def _ptr(t):
 
 
 # what EnvBatch.expand_rows returns: device tensors [M, K, ...] (dense None without the dense pair; parent_hash [M, 2])
+PLANE_SLACK = 1024  # readable bytes the library wants behind every plane it is given (ARCLE_PLANE_SLACK, include/arcle_hip.h)
 Expansion = collections.namedtuple("Expansion", "reward term status hash dense parent_hash")
 
 
@@ -111,8 +112,11 @@ class EnvBatch:
         self.PS = int(plane_stride)  # plane stride: one aligned dwordx4 per lane
         self.max_trial, self.kind = int(max_trial), kind
         # 16 B alignment of every plane/record row comes from torch's >=256 B allocation alignment
-        self.planes = {k: torch.zeros((self.N, self.PS), dtype=torch.int8, device=self.device)
-                       for k in KIND_PLANES[kind]}
+        # PLANE_SLACK bytes behind every plane (ARCLE_PLANE_SLACK): the row kernels request the answer plane from all 64 lanes — 1024
+        # bytes from the env's plane on, whatever the plane stride — and for the last envs of a handle with a stride below 1024 that
+        # is behind the plane: without the slack, behind the allocation, which may end a mapped region
+        self._plane_store = {k: torch.zeros(self.N * self.PS + PLANE_SLACK, dtype=torch.int8, device=self.device) for k in KIND_PLANES[kind]}
+        self.planes = {k: v[:self.N * self.PS].view(self.N, self.PS) for k, v in self._plane_store.items()}
         self.rec = torch.zeros((self.N, 16), dtype=torch.int8, device=self.device)
         self.cnt = torch.zeros((self.N, 2), dtype=torch.int32, device=self.device)
         self.reward = torch.zeros(self.N, dtype=torch.int32, device=self.device)
@@ -629,6 +633,43 @@ class EnvBatch:
         self._check(self.L.arcle_expand_rows(self._h, M, _ptr(rows), rows.stride(0), K, _lib.INGRESS[form], _ptr(payload), _ptr(op), stride,
                                              _ptr(src_env), _ptr(out.reward), _ptr(out.term), _ptr(out.status), _ptr(out.hash),
                                              _ptr(out.dense), _ptr(out.parent_hash), int(flags), self._stream()), "arcle_expand_rows")
+        return out
+
+    def expand_macros(self, rows, form, payload, op, length=None, src_env=None, dense=False, flags=0, out=None):
+        """K candidate MACROS per state row — sequences of up to T steps run back to back on the wave's register copy of the state —
+        with one set of verdicts per macro (arcle_expand_macros).  payload [K, T, w] with op int32 [K, T] and length int32 [K] (one
+        set for every row) or [M, K, T, w] with op [M, K, T] and length [M, K] (a set per row); w as in `expand_rows`; length None:
+        every macro runs its T steps.  Returns an Expansion, all [M, K, ...]: reward = the steps' rewards summed, term = the last
+        step's, status = the OR of the steps' status bits, dense = the pair after the last step, hash = the hash of the final row —
+        what `length` in-place transition_rows calls + hash_rows report.  A length outside [1, T] runs nothing: ARCLE_ST_BAD_OP,
+        the parent's hash.  out: an Expansion of a previous call with the same shapes (captured graphs)."""
+        assert form in ("bbox", "point", "bits"), "expand_macros takes bbox, point or bits actions"
+        M = int(rows.shape[0])
+        tw = {"bbox": 4, "point": 2, "bits": self.bits_stride}[form]
+        assert rows.dtype == torch.int8 and rows.dim() == 2 and rows.stride(1) == 1
+        assert payload.dtype == (torch.uint8 if form == "bits" else torch.int32) and payload.is_contiguous() and op.dtype == torch.int32 and op.is_contiguous()
+        if payload.dim() == 3:
+            K, T, stride = int(payload.shape[0]), int(payload.shape[1]), 0
+            assert tuple(payload.shape) == (K, T, tw) and tuple(op.shape) == (K, T)
+            lead = (K,)
+        else:
+            K, T = int(payload.shape[1]), int(payload.shape[2])
+            stride = K
+            assert tuple(payload.shape) == (M, K, T, tw) and tuple(op.shape) == (M, K, T)
+            lead = (M, K)
+        if length is not None:
+            assert length.dtype == torch.int32 and length.is_contiguous() and tuple(length.shape) == lead
+        if out is None:
+            dev = self.device
+            out = Expansion(torch.empty((M, K), dtype=torch.int32, device=dev), torch.empty((M, K), dtype=torch.uint8, device=dev),
+                            torch.empty((M, K), dtype=torch.uint8, device=dev), torch.empty((M, K, 2), dtype=torch.int64, device=dev),
+                            torch.empty((M, K, 2), dtype=torch.int32, device=dev) if dense else None,
+                            torch.empty((M, 2), dtype=torch.int64, device=dev))
+        assert tuple(out.reward.shape) == (M, K) and (out.dense is not None) == bool(dense)
+        self._check(self.L.arcle_expand_macros(self._h, M, _ptr(rows), rows.stride(0), K, T, _lib.INGRESS[form], _ptr(payload), _ptr(op),
+                                               _ptr(length), stride, _ptr(src_env), _ptr(out.reward), _ptr(out.term), _ptr(out.status),
+                                               _ptr(out.hash), _ptr(out.dense), _ptr(out.parent_hash), int(flags), self._stream()),
+                    "arcle_expand_macros")
         return out
 
     def components_rows(self, rows=None, max_components=32, skip_color=-1, bits=False, out=None):

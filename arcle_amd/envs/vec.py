@@ -602,6 +602,51 @@ class ARCVecEnv:
         fl = STEP_RESET_ON_SUBMIT if self.flags & STEP_RESET_ON_SUBMIT else 0
         return self.batch.expand_rows(rows, form, pay, op, src_env, dense=True, flags=fl)
 
+    def _macro_action(self, action):
+        if "bbox" in action:
+            form, pay = "bbox", action["bbox"].to(device=self.device, dtype=torch.int32).contiguous()
+        elif "point" in action:
+            form, pay = "point", action["point"].to(device=self.device, dtype=torch.int32).contiguous()
+        elif "bits" in action:
+            form, pay = "bits", action["bits"].to(device=self.device, dtype=torch.uint8).contiguous()
+        else:
+            raise ValueError("macros take bbox, point or bits actions")
+        op = action["operation"].to(device=self.device, dtype=torch.int32).contiguous()
+        length = action.get("length")
+        if length is not None:
+            length = length.to(device=self.device, dtype=torch.int32).contiguous()
+        return form, pay, op, length
+
+    def expand_macros(self, rows, action, src_env=None):
+        """K candidate MACROS per state row — sequences of up to T steps, e.g. Copy then Paste, judged as one candidate — without
+        materialising anything: `expand` with the step loop on the device.  action = {"bbox" | "point" | "bits": [K, T, ..] or
+        [M, K, T, ..], "operation": [K, T] or [M, K, T], "length": [K] or [M, K] (optional: every macro runs T steps)}.  Returns an
+        Expansion of [M, K, ...] tensors: reward (summed over the steps), term (the last step's), status (the OR of the steps' bits;
+        a length outside 1 .. T: ARCLE_ST_BAD_OP, the child is its parent), hash and dense of the state after the last step — each
+        equal to what `transition_macros` + `hash_rows` give for that (row, macro) pair.  This env's own state is not touched."""
+        if self._host_slots:
+            raise NotImplementedError("expand_macros needs a device-only op table (no host callables)")
+        form, pay, op, length = self._macro_action(action)
+        if src_env is not None:
+            src_env = src_env.to(device=self.device, dtype=torch.int32).contiguous()
+        fl = STEP_RESET_ON_SUBMIT if self.flags & STEP_RESET_ON_SUBMIT else 0
+        return self.batch.expand_macros(rows, form, pay, op, length, src_env, dense=True, flags=fl)
+
+    def transition_macros(self, rows, action, src_env=None):
+        """One macro per row, materialised: action = {form: [M, T, ..], "operation": [M, T], "length": [M] (optional)}.  Returns (rows
+        after each row's own macro [M, L], the steps' rewards summed int32 [M], the last step's terminated bool [M]).  T in-place
+        `transition` launches, launch t over the rows that still have a step at position t (`search.run_macros`): the way a search
+        materialises the few states it keeps, not its hot path."""
+        from ..search import run_macros
+        form, pay, op, length = self._macro_action(action)
+        if src_env is not None:
+            src_env = src_env.to(device=self.device, dtype=torch.int32).contiguous()
+        L = self.batch.state_row_size()
+        buf = torch.zeros((int(rows.shape[0]), (L + 15) & ~15), dtype=torch.int8, device=self.device)
+        buf[:, :L] = rows[:, :L]
+        out, reward, term = run_macros(lambda r, a, s: self.transition(r, a, s, in_place=True), buf, {form: pay, "operation": op, "length": length}, src_env)
+        return out[:, :L], reward, term
+
     def components(self, rows=None, max_components=32, skip_color=-1, bits=False):
         """The objects of every state's grid as ready-made actions — what a search proposes its candidates from (`arcle_amd.search`:
         object_actions, propose_objects).  rows int8 [M, L] (as `state_rows` / `transition` return them) or None = this env's own

@@ -114,16 +114,29 @@ def beam_search(venv, rows, actions, width, depth, src_env=None, propose=None):
     a per-state set names nothing.  Slots with operation -1 are padding: their children carry a status bit and are dropped.
     A propose that returns {"bits": uint8 [M, K, 128], "operation": ...} (`propose_objects(masks=True)`: each object's exact cells)
     makes the sequence a list of (selection, op), selection a bool NumPy array [H, W] (H, W = venv.H, venv.W): what the reference's
-    `step({"selection": selection, "operation": op})` takes."""
+    `step({"selection": selection, "operation": op})` takes.
+
+    Macro candidates — a "length" key in `actions` ({form: [K, T, w], "operation": [K, T], "length": [K]}) or in what `propose`
+    returns ([M, K, T, w], [M, K, T], [M, K]: `propose_object_macros`) — are sequences of up to T steps judged as ONE candidate: they
+    are expanded through `venv.expand_macros` and the kept ones materialised through `venv.transition_macros`, so a step whose own
+    effect the dense pair cannot see (a Copy before its Paste) is not lost at the width cut.  `counts` still counts children.  With
+    one shared set the sequence stays a list of indices into it; with `propose` it lists the PRIMITIVE steps in order, the first
+    `length` of every macro, in the forms above."""
     dev = rows.device
 
     def payload_of(a):
         form = "bbox" if "bbox" in a else "point" if "point" in a else "bits"
         return form, a[form].to(device=dev, dtype=torch.uint8 if form == "bits" else torch.int32).contiguous()
+    macro, length = False, None  # (macro candidates: decided by the "length" key of the first candidate set)
     if propose is None:
         form, pay = payload_of(actions)
         op = actions["operation"].to(device=dev, dtype=torch.int32).contiguous()
-        assert pay.dim() == 2 and op.dim() == 1, "beam_search takes one candidate set for every state"
+        macro = "length" in actions
+        if macro:
+            length = actions["length"].to(device=dev, dtype=torch.int32).contiguous()
+            assert pay.dim() == 3 and op.dim() == 2 and length.dim() == 1, "beam_search takes one set of macros for every state"
+        else:
+            assert pay.dim() == 2 and op.dim() == 1, "beam_search takes one candidate set for every state"
         K = int(op.shape[0])
     M0 = int(rows.shape[0])
     src = (torch.arange(M0, device=dev) if src_env is None else src_env.to(dev)).to(torch.int32)
@@ -141,11 +154,24 @@ def beam_search(venv, rows, actions, width, depth, src_env=None, propose=None):
             form, pay = payload_of(cand)
             assert form != "point", "propose returns bbox or bits candidates"
             op = cand["operation"].to(device=dev, dtype=torch.int32).contiguous()
-            assert pay.dim() == 3 and op.dim() == 2 and pay.shape[0] == M, "propose returns a candidate set per frontier row"
+            assert path is None or macro == ("length" in cand), "propose returns macros at every depth or at none"
+            macro = "length" in cand
+            if macro:
+                length = cand["length"].to(device=dev, dtype=torch.int32).contiguous()
+                assert pay.dim() == 4 and op.dim() == 3 and length.dim() == 2 and pay.shape[0] == M, "propose returns a set of macros per frontier row"
+                if path is None:  # a macro's slot in the path: its T steps' payloads side by side, [M, depth, T * w]
+                    path = torch.empty((M0, 0, pay.shape[2] * pay.shape[3]), dtype=pay.dtype, device=dev)
+                    path_op = torch.empty((M0, 0, pay.shape[2]), dtype=torch.int32, device=dev)
+                    path_len = torch.empty((M0, 0), dtype=torch.int32, device=dev)
+            else:
+                assert pay.dim() == 3 and op.dim() == 2 and pay.shape[0] == M, "propose returns a candidate set per frontier row"
             K = int(op.shape[1])
             if path is None:  # (shaped by the first candidate set: 4 int32 of a box, or the bytes of a bit row)
                 path = torch.empty((M0, 0, pay.shape[2]), dtype=pay.dtype, device=dev)
-        ex = venv.expand(frontier, {form: pay, "operation": op}, src)
+        if macro:
+            ex = venv.expand_macros(frontier, {form: pay, "operation": op, "length": length}, src)
+        else:
+            ex = venv.expand(frontier, {form: pay, "operation": op}, src)
         h = ex.hash[:, :, 0]
         ok = (ex.status == 0) & (h != ex.parent_hash[:, :1])
         idx = torch.nonzero(ok.reshape(-1)).reshape(-1)  # child index m * K + k, ascending
@@ -164,6 +190,13 @@ def beam_search(venv, rows, actions, width, depth, src_env=None, propose=None):
         parent, k = idx // K, idx % K
         if propose is None:
             step_pay, step_op, step = pay.index_select(0, k), op.index_select(0, k), k.reshape(-1, 1)
+            if macro:
+                step_len = length.index_select(0, k)
+        elif macro:  # the survivors' macros, gathered from their parents' sets: [n, T, w], [n, T], [n]
+            T = int(op.shape[2])
+            step_pay, step_op = pay.reshape(-1, T, pay.shape[3]).index_select(0, idx), op.reshape(-1, T).index_select(0, idx)
+            step_len = length.reshape(-1).index_select(0, idx)
+            step = step_pay.reshape(-1, 1, T * pay.shape[3])
         else:  # the survivors' actions, gathered from their parents' sets
             step_pay, step_op = pay.reshape(-1, pay.shape[2]).index_select(0, idx), op.reshape(-1).index_select(0, idx)
             step = step_pay.unsqueeze(1)
@@ -173,6 +206,17 @@ def beam_search(venv, rows, actions, width, depth, src_env=None, propose=None):
             counts.append((M * K, int(idx.numel()), 0))
             if propose is None:
                 seq = path[parent[g]].tolist() + [int(k[g])]
+            elif macro:  # the primitive steps: the first `length` of every macro on the way, in order
+                T, w_ = int(op.shape[2]), int(pay.shape[3])
+                sels = torch.cat([path[parent[g]], step[g]], 0).reshape(-1, T, w_)
+                ops = torch.cat([path_op[parent[g]], step_op[g:g + 1]], 0)
+                lens = torch.cat([path_len[parent[g]], step_len[g:g + 1]], 0).tolist()
+                took = [(d, t) for d, n in enumerate(lens) for t in range(n)]
+                if form == "bbox":
+                    seq = [tuple(sels[d, t].tolist()) + (int(ops[d, t]),) for d, t in took]
+                else:
+                    cells = unpack_bits(sels, venv.H, venv.W).cpu().numpy()
+                    seq = [(cells[d, t], int(ops[d, t])) for d, t in took]
             else:
                 sels, ops = torch.cat([path[parent[g]], step[g]], 0), torch.cat([path_op[parent[g]], step_op[g:g + 1]], 0).tolist()
                 if form == "bbox":
@@ -190,10 +234,17 @@ def beam_search(venv, rows, actions, width, depth, src_env=None, propose=None):
         if best.numel() == 0:
             break
         src_next = src.index_select(0, parent)
-        frontier, _, _ = venv.transition(frontier.index_select(0, parent), {form: step_pay.index_select(0, best), "operation": step_op.index_select(0, best)},
-                                         src_next)
+        if macro:
+            frontier, _, _ = venv.transition_macros(frontier.index_select(0, parent), {form: step_pay.index_select(0, best), "operation": step_op.index_select(0, best),
+                                                                                      "length": step_len.index_select(0, best)}, src_next)
+        else:
+            frontier, _, _ = venv.transition(frontier.index_select(0, parent), {form: step_pay.index_select(0, best), "operation": step_op.index_select(0, best)},
+                                             src_next)
         path = torch.cat([path.index_select(0, parent), step.index_select(0, best)], 1)
-        if propose is not None:
+        if propose is not None and macro:
+            path_op = torch.cat([path_op.index_select(0, parent), step_op.index_select(0, best).unsqueeze(1)], 1)
+            path_len = torch.cat([path_len.index_select(0, parent), step_len.index_select(0, best).reshape(-1, 1)], 1)
+        elif propose is not None:
             path_op = torch.cat([path_op.index_select(0, parent), step_op.index_select(0, best).reshape(-1, 1)], 1)
         root, src = root.index_select(0, parent), src_next
     return BeamResult(None, counts, None)
@@ -298,4 +349,78 @@ def propose_objects(box_ops, seed_ops, max_components=16, skip_color=0, masks=Fa
         comp = venv.components(rows, max_components=max_components, skip_color=skip_color, bits=True) if masks else \
             venv.components(rows, max_components=max_components, skip_color=skip_color)
         return object_actions(comp, box_ops, seed_ops, masks)
+    return propose
+
+
+def run_macros(transition, rows, action, src_env=None):
+    """One macro per row, materialised: `rows` [M, L] after each row's own macro — action = {form: [M, T, w], "operation": [M, T],
+    "length": [M] (optional: every row runs T steps)} — by T calls of `transition(rows_t, action_t, src_t) -> (rows, reward, term)`
+    (`ARCVecEnv.transition`'s signature), call t over the rows that still have a step at position t.  -> (rows, reward int32 [M] =
+    the steps' rewards summed, terminated bool [M] = the last step's).  A length outside [1, T] runs nothing, as `expand_macros`
+    reports it.  The gathers are bounded by the beam width: this is how a search materialises its survivors, not its hot path."""
+    form = "bbox" if "bbox" in action else "point" if "point" in action else "bits"
+    pay, op, length = action[form], action["operation"], action.get("length")
+    M, T = int(op.shape[0]), int(op.shape[1])
+    cur = rows.clone()
+    reward = torch.zeros(M, dtype=torch.int32, device=rows.device)
+    term = torch.zeros(M, dtype=torch.bool, device=rows.device)
+    for t in range(T):
+        if length is None:
+            out, r, tm = transition(cur, {form: pay[:, t].contiguous(), "operation": op[:, t].contiguous()}, src_env)
+            cur, reward, term = out, reward + r.to(torch.int32), tm.to(torch.bool)
+            continue
+        idx = torch.nonzero((length > t) & (length <= T)).reshape(-1)
+        if idx.numel() == 0:
+            break
+        out, r, tm = transition(cur.index_select(0, idx), {form: pay[:, t].index_select(0, idx), "operation": op[:, t].index_select(0, idx)},
+                                None if src_env is None else src_env.index_select(0, idx))
+        cur[:, :out.shape[1]].index_copy_(0, idx, out.to(cur.dtype))
+        reward.index_add_(0, idx, r.to(torch.int32))
+        term.index_copy_(0, idx, tm.to(torch.bool))
+    return cur, reward, term
+
+
+def object_macros(comp, box_ops, seed_ops, pair_ops):
+    """The components of M states as a set of MACROS per state (T = 2 when pair_ops is not empty, else 1): {"bbox": int32 [M, K, T, 4],
+    "operation": int32 [M, K, T], "length": int32 [M, K]}.  First the singles of `object_actions(comp, box_ops, seed_ops)`, in its
+    order, as macros of length 1; then for every ordered pair of components (i, j), i-major, and every (op_a, op_b) of pair_ops the
+    macro [op_a on box i, op_b on box j] of length 2 — CopyO on one object's box, Paste at another's; a selection-setting op, then
+    an object op — K = C * (len(box_ops) + len(seed_ops)) + C * C * len(pair_ops).  Pair slots with i == j or a component >= count
+    get operation -1 at step 0 and length 1: one ARCLE_ST_BAD_OP child, dropped by beam_search.  Boxes only.  Pure indexing on the
+    device: no host synchronisation."""
+    single = object_actions(comp, box_ops, seed_ops)
+    box, count = comp.box, comp.count
+    M, C = int(box.shape[0]), int(box.shape[1])
+    dev = box.device
+    T = 2 if len(pair_ops) else 1
+    K1, npair = int(single["operation"].shape[1]), len(pair_ops)
+    bb1 = torch.zeros((M, K1, T, 4), dtype=torch.int32, device=dev)
+    bb1[:, :, 0] = single["bbox"]
+    op1 = torch.full((M, K1, T), -1, dtype=torch.int32, device=dev)
+    op1[:, :, 0] = single["operation"]
+    len1 = torch.ones((M, K1), dtype=torch.int32, device=dev)
+    if not npair:
+        return {"bbox": bb1, "operation": op1, "length": len1}
+    po = torch.as_tensor(list(pair_ops), dtype=torch.int32, device=dev).reshape(npair, 2)
+    ar = torch.arange(C, device=dev)
+    there = ar.reshape(1, C) < count.reshape(M, 1)
+    ok = (there.reshape(M, C, 1) & there.reshape(M, 1, C) & (ar.reshape(C, 1) != ar.reshape(1, C)).reshape(1, C, C)).reshape(M, C, C, 1)
+    b32 = box.to(torch.int32)
+    bb2 = torch.stack([b32.reshape(M, C, 1, 1, 4).expand(M, C, C, npair, 4), b32.reshape(M, 1, C, 1, 4).expand(M, C, C, npair, 4)], 4)
+    bb2 = torch.where(ok.reshape(M, C, C, 1, 1, 1), bb2, torch.zeros((), dtype=torch.int32, device=dev))
+    op2 = torch.where(ok.reshape(M, C, C, 1, 1), po.reshape(1, 1, 1, npair, 2), torch.full((), -1, dtype=torch.int32, device=dev))
+    len2 = torch.where(ok, torch.full((), 2, dtype=torch.int32, device=dev), torch.ones((), dtype=torch.int32, device=dev)).expand(M, C, C, npair)
+    K2 = C * C * npair
+    return {"bbox": torch.cat([bb1, bb2.reshape(M, K2, 2, 4)], 1).contiguous(), "operation": torch.cat([op1, op2.reshape(M, K2, 2)], 1).contiguous(),
+            "length": torch.cat([len1, len2.reshape(M, K2)], 1).contiguous()}
+
+
+def propose_object_macros(box_ops, seed_ops, pair_ops, max_components=16, skip_color=0):
+    """A `propose` for beam_search that returns macros: at every depth the components of each frontier state's grid (`venv.components`,
+    one launch) as `object_macros` arranges them — the singles of `propose_objects`, then every (op_a, op_b) of pair_ops on every
+    ordered pair of objects' boxes as ONE candidate of two steps."""
+    box_ops, seed_ops, pair_ops = list(box_ops), list(seed_ops), [tuple(p) for p in pair_ops]
+
+    def propose(venv, rows):
+        return object_macros(venv.components(rows, max_components=max_components, skip_color=skip_color), box_ops, seed_ops, pair_ops)
     return propose

@@ -38,11 +38,13 @@
 extern "C" {
 #endif
 
-#define ARCLE_ABI_VERSION 9
+#define ARCLE_ABI_VERSION 10
 #define ARCLE_MAX_OPS 64
 #define ARCLE_MAX_CELLS 1024 /* H*W <= 1024: one 64-lane wavefront x 16 cells holds a plane (the one-wavefront-per-env kernels);
                                 larger planes (H, W <= 127) are served by the workgroup-per-env kernels — see "Grids beyond
                                 ARCLE_MAX_CELLS" below */
+#define ARCLE_PLANE_SLACK 1024 /* readable bytes wanted BEHIND the answer plane's n_envs * plane_stride (the library's own planes all have
+                                  them): arcle_transition_rows requests that plane from all 64 lanes, 1024 bytes from the env's plane on */
 #define ARCLE_MAX_SIDE 127   /* H, W <= 127: grid dims are int8 in the record (and in the reference's state dict, base.py:162-166) */
 /* default per-env plane stride: H*W rounded up to a whole number of 128-byte lines (30x30 -> 1024 B), so that no two
  * envs share a cache line of a plane and every plane store writes full lines */
@@ -220,7 +222,10 @@ typedef struct arcle_env arcle_env; /* opaque handle */
 
 /* Creates a handle. `bufs` are caller-owned device buffers (e.g. torch tensors' data_ptr);
  * if bufs == NULL the library allocates all planes itself (hipMalloc) and frees them in
- * arcle_destroy. Replaces AbstractARCEnv.__init__ state allocation (base.py:37-66). */
+ * arcle_destroy. Replaces AbstractARCEnv.__init__ state allocation (base.py:37-66).
+ * A caller-owned answer plane with plane_stride < 1024 must be followed by ARCLE_PLANE_SLACK - plane_stride readable bytes (any
+ * content, never written): arcle_transition_rows reads 1024 bytes from the env's plane on whatever the stride, so for the handle's
+ * last envs it reads behind the plane (arcle_amd.engine.EnvBatch allocates every plane with that slack). */
 int arcle_create(const arcle_config* cfg, const arcle_buffers* bufs, arcle_env** out);
 int arcle_destroy(arcle_env* env);
 /* Fills `out` with the device pointers the handle uses. */
@@ -486,6 +491,24 @@ int arcle_expand_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_
                       const void* sel, const int32_t* op, int32_t action_row_stride, const int32_t* src_env, int32_t* reward,
                       uint8_t* term, uint8_t* status, uint64_t* hash, int32_t* dense, uint64_t* parent_hash, uint32_t flags,
                       void* stream);
+/* arcle_expand_macros: K = n_actions MACROS per state row, a macro being a sequence of up to T = max_len steps; nothing but one set of
+ * verdicts per macro is written.  sel is [..][K][T][w] (w = 4 int32 for ARCLE_INGRESS_BBOX, 2 int32 for ARCLE_INGRESS_POINT,
+ * arcle_mask_bits_stride() bytes for ARCLE_INGRESS_BITS) and op int32 [..][K][T]; len int32 [..][K] = the steps macro k runs (steps
+ * len .. T-1 of its slot are not read), NULL: every macro runs T; action_row_stride = 0: ONE set of K macros for every row, = n_actions:
+ * a set per row, which sel, op and len all follow.  For every (m, k) the outputs equal what len[m, k] successive IN-PLACE
+ * arcle_transition_rows calls report for (row m, steps 0 .. len-1 of macro (m, k), src_env[m], same flags): reward = the sum of the
+ * steps' rewards, term = the last step's, status = the OR of the steps' status bits (a step that raises ARCLE_ST_BAD_OP or
+ * _ROTATE_DOMAIN did not happen; the steps after it still run), dense = the pair the last step reports ((0, 0) if that step did not
+ * happen), hash = arcle_hash_rows of the final row.  With max_len = 1 and len NULL the call is arcle_expand_rows, output for output.
+ * A len outside [1, T] gives that child ARCLE_ST_BAD_OP and runs no step: its hash is the parent's, reward, term and dense are 0 —
+ * as for a row whose src_env names no env (ARCLE_ST_BAD_TASK).  Refusals as arcle_expand_rows: int8 masks and ARCLE_INGRESS_BBOX5,
+ * bit rows that are not 2-byte aligned, flags other than ARCLE_STEP_RESET_ON_SUBMIT | _DENSE, max_len < 1 or n_rows * n_actions *
+ * max_len >= 2^28 (ARCLE_ERR_ARG); handles of more than ARCLE_MAX_CELLS cells per plane (ARCLE_ERR_CONFIG).  Nothing of the handle is
+ * touched — sticky status word, resident envs, counters, dense cache, installed outputs.  Allocates nothing: may be captured. */
+int arcle_expand_macros(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t n_actions, int32_t max_len, int ingress,
+                        const void* sel, const int32_t* op, const int32_t* len, int32_t action_row_stride, const int32_t* src_env,
+                        int32_t* reward, uint8_t* term, uint8_t* status, uint64_t* hash, int32_t* dense, uint64_t* parent_hash,
+                        uint32_t flags, void* stream);
 /* Connected components (color.py:8-30: 4-connected, same colour, inside grid_dim) of the grid of every state row, each as a ready-made
  * BBoxWrapper / PointWrapper action: what a search proposes its candidate actions from (arcle_expand_rows takes a set per row).
  * rows == NULL: the resident envs 0 .. n_rows-1 (n_rows <= n_envs); else rows as for arcle_hash_rows (any alignment, stride >= the
