@@ -215,6 +215,7 @@ ARCLE_DEV void touch_args(const void* a, const void* b) { asm volatile("" ::"s"(
 #include "arcle_group.h"       // the deal of a self-ordering launch: slot -> env and its inputs (arcle::deal_group)
 #include "arcle_search.h"      // state hash + K-actions-per-row expansion (arcle_hash_rows / arcle_expand_rows)
 #include "arcle_components.h"  // connected components of a row's grid as candidate actions (arcle_components_rows)
+#include "arcle_objects.h"     // ... under the multi-colour / 8-connected notions of an object (arcle_objects_rows)
 #include "arcle_big_params.h"  // grids beyond ARCLE_MAX_CELLS: one workgroup per env (arcle_big.hip)
 
 using arcle::StepParams;
@@ -505,6 +506,14 @@ __global__ __launch_bounds__(64 * COMP_WAVES_PER_WG) void arcle_components_kerne
   const int row = wave_of_launch(COMP_WAVES_PER_WG);
   if (row >= x.p.n_envs) return;
   arcle::wave_components_row<FW>(x, nullptr, nullptr, row, (int)(threadIdx.x & 63));
+}
+
+// arcle_objects_rows: the same launch shape; MODE = ARCLE_OBJ_ANY_COLOR | ARCLE_OBJ_DIAG is a template parameter (no per-pass branches)
+template <int FW, int MODE>
+__global__ __launch_bounds__(64 * COMP_WAVES_PER_WG) void arcle_objects_kernel(const arcle::ObjParams x) {
+  const int row = wave_of_launch(COMP_WAVES_PER_WG);
+  if (row >= x.c.p.n_envs) return;
+  arcle::wave_objects_row<FW, MODE>(x, nullptr, nullptr, row, (int)(threadIdx.x & 63));
 }
 
 __global__ __launch_bounds__(64 * WAVES_PER_WG) void arcle_reset_kernel(const StepParams p) {
@@ -2179,6 +2188,49 @@ extern "C" int arcle_components_rows(arcle_env* e, int32_t n_rows, const int8_t*
   const dim3 g = grid_for(n_rows, COMP_WAVES_PER_WG), b(64 * COMP_WAVES_PER_WG);
   if (width_class(e->base) != arcle::FW_GENERIC) hipLaunchKernelGGL(arcle_components_kernel<arcle::FW_FAST>, g, b, 0, (hipStream_t)stream, x);
   else hipLaunchKernelGGL(arcle_components_kernel<arcle::FW_GENERIC>, g, b, 0, (hipStream_t)stream, x);
+  HIP_TRY(e, hipGetLastError());
+  return ARCLE_OK;
+}
+
+// arcle_components_rows with a notion of "object" (arcle_objects.h) and the optional colour sets.  mode 0 without `colors` IS
+// arcle_components_rows: the same kernel, launched by the same code.
+template <int FW>
+static void launch_objects(uint32_t mode, const dim3& g, const dim3& b, hipStream_t stream, const arcle::ObjParams& x) {
+  switch (mode) {
+    case 0: hipLaunchKernelGGL((arcle_objects_kernel<FW, 0>), g, b, 0, stream, x); break;
+    case 1: hipLaunchKernelGGL((arcle_objects_kernel<FW, 1>), g, b, 0, stream, x); break;
+    case 2: hipLaunchKernelGGL((arcle_objects_kernel<FW, 2>), g, b, 0, stream, x); break;
+    default: hipLaunchKernelGGL((arcle_objects_kernel<FW, 3>), g, b, 0, stream, x); break;
+  }
+}
+extern "C" int arcle_objects_rows(arcle_env* e, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, int32_t skip_color,
+                                  uint32_t mode, int32_t* count, int32_t* comp, uint8_t* bits, uint32_t* colors, void* stream) {
+  if (!e || !count || !comp) return ARCLE_ERR_ARG;
+  if (mode & ~(ARCLE_OBJ_ANY_COLOR | ARCLE_OBJ_DIAG)) return fail(e, ARCLE_ERR_ARG, "arcle_objects_rows: mode is ARCLE_OBJ_ANY_COLOR | ARCLE_OBJ_DIAG");
+  if (mode == 0 && !colors) return arcle_components_rows(e, n_rows, rows, stride, max_comp, skip_color, count, comp, bits, stream);
+  if (n_rows <= 0) return fail(e, ARCLE_ERR_ARG, "n_rows must be positive");
+  if (e->big) return fail(e, ARCLE_ERR_CONFIG, "arcle_objects_rows: handles of at most 1024 cells per plane (ARCLE_MAX_CELLS)");
+  if (max_comp < 1 || max_comp > ARCLE_MAX_CELLS) return fail(e, ARCLE_ERR_ARG, "arcle_objects_rows: max_comp in [1, ARCLE_MAX_CELLS]");
+  if (rows) {
+    if (int rc = check_rows(e, rows, stride, 0)) return rc;
+  } else if (n_rows > e->cfg.n_envs) {
+    return fail(e, ARCLE_ERR_ARG, "arcle_objects_rows: rows == NULL labels the resident envs (n_rows <= n_envs)");
+  }
+  DeviceGuard guard(e->device);
+  arcle::ObjParams x = {};
+  x.c.p = e->base;
+  x.c.p.n_envs = n_rows;
+  x.c.p.rows_in = rows;
+  x.c.p.rows_in_stride = rows ? stride : 0;
+  x.c.max_comp = max_comp;
+  x.c.skip_color = skip_color < 0 ? -1 : skip_color;
+  x.c.count = count;
+  x.c.comp = comp;
+  x.c.bits = bits;
+  x.colors = colors;
+  const dim3 g = grid_for(n_rows, COMP_WAVES_PER_WG), b(64 * COMP_WAVES_PER_WG);
+  if (width_class(e->base) != arcle::FW_GENERIC) launch_objects<arcle::FW_FAST>(mode, g, b, (hipStream_t)stream, x);
+  else launch_objects<arcle::FW_GENERIC>(mode, g, b, (hipStream_t)stream, x);
   HIP_TRY(e, hipGetLastError());
   return ARCLE_OK;
 }

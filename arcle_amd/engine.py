@@ -698,6 +698,34 @@ class EnvBatch:
                     "arcle_components_rows")
         return out
 
+    def objects_rows(self, rows=None, max_components=32, skip_color=-1, any_color=False, diagonal=False, bits=False, colors=False, out=None):
+        """`components_rows` under a chosen notion of "object" (arcle_objects_rows): any_color — every cell inside grid_dim that is not
+        of skip_color may join, so an object may have several colours (skip_color -1: a full rectangle is one object); diagonal —
+        8-connected.  Neither: the components of `components_rows`, output for output.  Returns (count, comp, bits | None, colors
+        uint32-as-int32 [M, C] | None): everything as `components_rows` (comp[..., 6] is the SEED's colour); colors[m, k] has bit
+        v & 31 set for every cell byte v of object k — for ARC's colours the set of colours present — and is not written for
+        k >= written.  out: the 4-tuple of a previous call with the same shapes.  Nothing of the batch is touched."""
+        C = int(max_components)
+        if rows is None:
+            M, ptr, stride = self.N, None, 0
+        else:
+            assert rows.dtype == torch.int8 and rows.dim() == 2 and rows.stride(1) == 1
+            M, ptr, stride = int(rows.shape[0]), _ptr(rows), rows.stride(0)
+        if out is None:
+            dev = self.device
+            out = (torch.zeros((M, 2), dtype=torch.int32, device=dev), torch.zeros((M, C, 8), dtype=torch.int32, device=dev),
+                   torch.zeros((M, C, _lib.BITS_STRIDE), dtype=torch.uint8, device=dev) if bits else None,
+                   torch.zeros((M, C), dtype=torch.int32, device=dev) if colors else None)
+        count, comp, mbits, cols = out
+        assert count.dtype == torch.int32 and tuple(count.shape) == (M, 2) and count.is_contiguous()
+        assert comp.dtype == torch.int32 and tuple(comp.shape) == (M, C, 8) and comp.is_contiguous()
+        assert (mbits is not None) == bool(bits) and (mbits is None or (mbits.dtype == torch.uint8 and tuple(mbits.shape) == (M, C, _lib.BITS_STRIDE) and mbits.is_contiguous()))
+        assert (cols is not None) == bool(colors) and (cols is None or (cols.dtype == torch.int32 and tuple(cols.shape) == (M, C) and cols.is_contiguous()))
+        mode = (_lib.OBJ_ANY_COLOR if any_color else 0) | (_lib.OBJ_DIAG if diagonal else 0)
+        self._check(self.L.arcle_objects_rows(self._h, M, ptr, stride, C, int(skip_color), mode, _ptr(count), _ptr(comp), _ptr(mbits), _ptr(cols),
+                                              self._stream()), "arcle_objects_rows")
+        return out
+
     def get_plane(self, name, out=None):
         """One key of the state dict as a dense [N, H, W] int8 array (device tensor, or a pinned host tensor passed as `out`):
         arcle_get_plane, a strided copy on the current stream."""

@@ -25,6 +25,8 @@ from ..engine import (AUG_PERMUTE, AUG_ROT90, EnvBatch, capture_guard, STEP_AUTO
 
 # what ARCVecEnv.components returns: views of one int32 [M, C, 8] buffer (+ the count pair, + the optional bit masks)
 Components = collections.namedtuple("Components", "count left box seed color cells bits")
+# what ARCVecEnv.objects returns: a Components with the colour set of every object (the fields object_actions / object_macros read are the same)
+Objects = collections.namedtuple("Objects", "count left box seed color cells bits colors")
 
 
 def _table_of(env_cls, **ctor_kw):
@@ -658,6 +660,16 @@ class ARCVecEnv:
         skip_color (-1: none; 0: ARC's background) belong to none.  Entries k >= count[m] are zero.  This env's state is not touched."""
         count, comp, mbits = self.batch.components_rows(rows, max_components, skip_color, bits)
         return Components(count[:, 0], count[:, 1], comp[:, :, 0:4], comp[:, :, 4:6], comp[:, :, 6], comp[:, :, 7], mbits)
+
+    def objects(self, rows=None, max_components=32, skip_color=-1, any_color=False, diagonal=False, bits=False, colors=False):
+        """`components` under a chosen notion of "object" (arcle_objects_rows, one launch): any_color — cells of different colours
+        join into one object (every cell inside grid_dim that is not of skip_color is a member: a two-colour shape on background 0
+        with skip_color=0 is ONE object) —, diagonal — 8-connected: a diagonal line is one object.  Neither: exactly `components`.
+        Returns an Objects: the fields of Components with the same meaning (color = the seed's colour) and colors [M, C] int32 or
+        None: bit c set for every colour c the object has a cell of.  `search.object_actions` / `object_macros` take it as they take
+        a Components.  This env's state is not touched."""
+        count, comp, mbits, cols = self.batch.objects_rows(rows, max_components, skip_color, any_color, diagonal, bits, colors)
+        return Objects(count[:, 0], count[:, 1], comp[:, :, 0:4], comp[:, :, 4:6], comp[:, :, 6], comp[:, :, 7], mbits, cols)
 
     def autotune(self, payload, operation=None, form="bbox"):
         """Times every launch plan the library has for this env's steps (self-ordering or not, the cache policies of the speculative grid

@@ -251,12 +251,14 @@ def beam_search(venv, rows, actions, width, depth, src_env=None, propose=None):
 
 
 # ---- the objects of a grid as candidate actions ------------------------------------------------------------------------------------
-def components_numpy(grid, grid_dim, max_components, skip_color=-1):
+def components_numpy(grid, grid_dim, max_components, skip_color=-1, any_color=False, diagonal=False):
     """The connected components of ONE grid as arcle_components_rows reports them (include/arcle_hip.h) — the host mirror the tests
     pin the device against, and pin against the reference's `dfs` (color.py:8-30): 4-connected cells of the same colour inside
     grid_dim, in ascending row-major index of their first cell (the seed); cells of `skip_color` (-1: none) belong to no component.
     grid int8 [H, W]; -> (count, left, comp int32 [C, 8] = x0, y0, x1, y1, sx, sy, colour, cells (rows >= count zero),
-    masks uint8 [C, H, W]), left = the cells inside grid_dim, not of skip_color, in no written component."""
+    masks uint8 [C, H, W]), left = the cells inside grid_dim, not of skip_color, in no written component.
+    any_color / diagonal: the objects of arcle_objects_rows instead — cells of any colour but skip_color join / the eight neighbours
+    of a cell count, not four; the colour reported is the seed's (`component_colors_numpy` gives the set)."""
     grid = np.asarray(grid)
     H, W = grid.shape
     gh, gw = min(int(grid_dim[0]), H), min(int(grid_dim[1]), W)
@@ -276,8 +278,9 @@ def components_numpy(grid, grid_dim, max_components, skip_color=-1):
             while queue:
                 x, y = queue.popleft()
                 cells.append((x, y))
-                for xn, yn in ((x - 1, y), (x + 1, y), (x, y - 1), (x, y + 1)):
-                    if 0 <= xn < gh and 0 <= yn < gw and todo[xn, yn] and grid[xn, yn] == col:
+                for xn, yn in _STRAIGHTS + (_DIAGONALS if diagonal else ()):
+                    xn, yn = x + xn, y + yn
+                    if 0 <= xn < gh and 0 <= yn < gw and todo[xn, yn] and (any_color or grid[xn, yn] == col):
                         todo[xn, yn] = False
                         queue.append((xn, yn))
             xs, ys = np.array(cells).T
@@ -285,6 +288,16 @@ def components_numpy(grid, grid_dim, max_components, skip_color=-1):
             comp[n] = (xs.min(), ys.min(), xs.max(), ys.max(), sx, sy, int(col), len(cells))
             n += 1
     return n, int(todo.sum()), comp, masks
+
+
+_STRAIGHTS, _DIAGONALS = ((-1, 0), (1, 0), (0, -1), (0, 1)), ((-1, -1), (-1, 1), (1, -1), (1, 1))
+
+
+def component_colors_numpy(grid, masks):
+    """The `colors` words of arcle_objects_rows for the masks uint8 [n, H, W] `components_numpy` returned: bit v & 31 for the byte v
+    (taken as unsigned) of every cell of the object.  -> uint32 [n]"""
+    bit = np.uint32(1) << (np.asarray(grid).astype(np.uint8) & 31).astype(np.uint32)
+    return np.array([np.bitwise_or.reduce(bit[np.asarray(m) != 0], initial=np.uint32(0)) for m in masks], np.uint32).reshape(len(masks))
 
 
 def pack_bits(masks):
@@ -339,15 +352,18 @@ def object_actions(comp, box_ops, seed_ops, masks=False):
     return {"bbox": bb.reshape(M, C * per, 4).contiguous(), "operation": op.reshape(M, C * per).to(torch.int32).contiguous()}
 
 
-def propose_objects(box_ops, seed_ops, max_components=16, skip_color=0, masks=False):
+def propose_objects(box_ops, seed_ops, max_components=16, skip_color=0, masks=False, any_color=False, diagonal=False):
     """A `propose` for beam_search: at every depth the connected components of each frontier state's grid (`venv.components`, one
     launch) with box_ops on their boxes and seed_ops on their seeds (`object_actions`); masks=True: on their exact cells, as bit
-    rows, instead of their boxes."""
+    rows, instead of their boxes.  any_color / diagonal: the multi-colour / 8-connected objects of `venv.objects` instead."""
     box_ops, seed_ops = list(box_ops), list(seed_ops)
 
     def propose(venv, rows):
-        comp = venv.components(rows, max_components=max_components, skip_color=skip_color, bits=True) if masks else \
-            venv.components(rows, max_components=max_components, skip_color=skip_color)
+        if any_color or diagonal:
+            comp = venv.objects(rows, max_components=max_components, skip_color=skip_color, any_color=any_color, diagonal=diagonal, bits=bool(masks))
+        else:
+            comp = venv.components(rows, max_components=max_components, skip_color=skip_color, bits=True) if masks else \
+                venv.components(rows, max_components=max_components, skip_color=skip_color)
         return object_actions(comp, box_ops, seed_ops, masks)
     return propose
 
@@ -415,12 +431,15 @@ def object_macros(comp, box_ops, seed_ops, pair_ops):
             "length": torch.cat([len1, len2.reshape(M, K2)], 1).contiguous()}
 
 
-def propose_object_macros(box_ops, seed_ops, pair_ops, max_components=16, skip_color=0):
+def propose_object_macros(box_ops, seed_ops, pair_ops, max_components=16, skip_color=0, any_color=False, diagonal=False):
     """A `propose` for beam_search that returns macros: at every depth the components of each frontier state's grid (`venv.components`,
     one launch) as `object_macros` arranges them — the singles of `propose_objects`, then every (op_a, op_b) of pair_ops on every
-    ordered pair of objects' boxes as ONE candidate of two steps."""
+    ordered pair of objects' boxes as ONE candidate of two steps.  any_color / diagonal: the objects of `venv.objects` instead."""
     box_ops, seed_ops, pair_ops = list(box_ops), list(seed_ops), [tuple(p) for p in pair_ops]
 
     def propose(venv, rows):
+        if any_color or diagonal:
+            return object_macros(venv.objects(rows, max_components=max_components, skip_color=skip_color, any_color=any_color, diagonal=diagonal),
+                                 box_ops, seed_ops, pair_ops)
         return object_macros(venv.components(rows, max_components=max_components, skip_color=skip_color), box_ops, seed_ops, pair_ops)
     return propose

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ARCLE_ABI_VERSION 10
+#define ARCLE_ABI_VERSION 11
 #define ARCLE_MAX_OPS 64
 #define ARCLE_MAX_CELLS 1024 /* H*W <= 1024: one 64-lane wavefront x 16 cells holds a plane (the one-wavefront-per-env kernels);
                                 larger planes (H, W <= 127) are served by the workgroup-per-env kernels — see "Grids beyond
@@ -526,6 +526,21 @@ int arcle_expand_macros(arcle_env* env, int32_t n_rows, const int8_t* rows, int3
  * below the row length or rows == NULL with n_rows > n_envs: ARCLE_ERR_ARG.  One wavefront per row; allocates nothing: may be captured. */
 int arcle_components_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, int32_t skip_color,
                           int32_t* count, int32_t* comp, uint8_t* bits, void* stream);
+/* The objects of the grid of every state row under a chosen notion of "object": arcle_components_rows with a `mode` and an optional
+ * set of colours per object.  Everything arcle_components_rows promises holds — the layout of count / comp / bits, rows == NULL, the
+ * order (ascending row-major index of the first cell, which is the seed: x0 == sx), `left`, entries k >= written not written at all,
+ * the refusals, no side effects, no allocation (may be captured), one wavefront per row, at most ARCLE_MAX_CELLS cells.
+ *   mode   0: the components of arcle_components_rows, output for output.  ARCLE_OBJ_ANY_COLOR: every cell inside grid_dim whose
+ *          colour is not skip_color may join — multi-colour objects (with skip_color == -1 a full rectangle is ONE object).
+ *          ARCLE_OBJ_DIAG: 8-connected, (x, y) ~ (x', y') iff max(|x - x'|, |y - y'|) == 1.  Both may be set; any other bit:
+ *          ARCLE_ERR_ARG.  comp[..][6] is the SEED's colour in every mode.
+ *   colors optional uint32 [n_rows][max_comp]: bit v & 31 is set for every cell of the object, v the cell's byte taken as unsigned
+ *          (for ARC's colours 0-9: the set of colours present; exactly one bit without ARCLE_OBJ_ANY_COLOR).  Entries k >= written
+ *          are not written. */
+#define ARCLE_OBJ_ANY_COLOR 1u
+#define ARCLE_OBJ_DIAG 2u
+int arcle_objects_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, int32_t skip_color,
+                       uint32_t mode, int32_t* count, int32_t* comp, uint8_t* bits, uint32_t* colors, void* stream);
 /* One state plane as a dense [n_envs][H*W] int8 array (device or pinned host memory), a strided copy on the stream: the
  * get_state()/set_state() of single keys of the reference's state dict. */
 int arcle_get_plane(arcle_env* env, int plane, int8_t* dst, void* stream);
