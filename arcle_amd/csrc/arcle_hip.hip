@@ -216,6 +216,7 @@ ARCLE_DEV void touch_args(const void* a, const void* b) { asm volatile("" ::"s"(
 #include "arcle_search.h"      // state hash + K-actions-per-row expansion (arcle_hash_rows / arcle_expand_rows)
 #include "arcle_components.h"  // connected components of a row's grid as candidate actions (arcle_components_rows)
 #include "arcle_objects.h"     // ... under the multi-colour / 8-connected notions of an object (arcle_objects_rows)
+#include "arcle_place.h"       // the translation at which each object best fits the answer (arcle_place_rows)
 #include "arcle_big_params.h"  // grids beyond ARCLE_MAX_CELLS: one workgroup per env (arcle_big.hip)
 
 using arcle::StepParams;
@@ -514,6 +515,14 @@ __global__ __launch_bounds__(64 * COMP_WAVES_PER_WG) void arcle_objects_kernel(c
   const int row = wave_of_launch(COMP_WAVES_PER_WG);
   if (row >= x.c.p.n_envs) return;
   arcle::wave_objects_row<FW, MODE>(x, nullptr, nullptr, row, (int)(threadIdx.x & 63));
+}
+
+// arcle_place_rows: the same launch shape (one wavefront per row, every object of the row in turn; no LDS)
+template <int FW>
+__global__ __launch_bounds__(64 * COMP_WAVES_PER_WG) void arcle_place_kernel(const arcle::PlaceParams x) {
+  const int row = wave_of_launch(COMP_WAVES_PER_WG);
+  if (row >= x.p.n_envs) return;
+  arcle::wave_place_row<FW>(x, nullptr, nullptr, row, (int)(threadIdx.x & 63));
 }
 
 __global__ __launch_bounds__(64 * WAVES_PER_WG) void arcle_reset_kernel(const StepParams p) {
@@ -2231,6 +2240,43 @@ extern "C" int arcle_objects_rows(arcle_env* e, int32_t n_rows, const int8_t* ro
   const dim3 g = grid_for(n_rows, COMP_WAVES_PER_WG), b(64 * COMP_WAVES_PER_WG);
   if (width_class(e->base) != arcle::FW_GENERIC) launch_objects<arcle::FW_FAST>(mode, g, b, (hipStream_t)stream, x);
   else launch_objects<arcle::FW_GENERIC>(mode, g, b, (hipStream_t)stream, x);
+  HIP_TRY(e, hipGetLastError());
+  return ARCLE_OK;
+}
+
+// the best translation of every object of every row (arcle_place.h): reads the rows (or the resident grid planes and records), the
+// objects' bit rows and the answer planes, writes the caller's arrays — nothing of the handle is written
+extern "C" int arcle_place_rows(arcle_env* e, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, const int32_t* count,
+                                const uint8_t* bits, const int32_t* src_env, int32_t max_dist, int32_t* place, int32_t* base, void* stream) {
+  if (!e || !bits || !place) return ARCLE_ERR_ARG;
+  if (n_rows <= 0) return fail(e, ARCLE_ERR_ARG, "n_rows must be positive");
+  if (e->big) return fail(e, ARCLE_ERR_CONFIG, "arcle_place_rows: handles of at most 1024 cells per plane (ARCLE_MAX_CELLS)");
+  if (!e->bufs.plane[ARCLE_PL_ANSWER]) return fail(e, ARCLE_ERR_CONFIG, "arcle_place_rows needs the answer plane");
+  if (max_comp < 1 || max_comp > ARCLE_MAX_CELLS) return fail(e, ARCLE_ERR_ARG, "arcle_place_rows: max_comp in [1, ARCLE_MAX_CELLS]");
+  if (max_dist < 0) return fail(e, ARCLE_ERR_ARG, "arcle_place_rows: max_dist must not be negative");
+  if ((uintptr_t)bits & 1u) return fail(e, ARCLE_ERR_ARG, "arcle_place_rows: bit rows must be 2-byte aligned");
+  if (rows) {
+    if (int rc = check_rows(e, rows, stride, 0)) return rc;
+  } else if (n_rows > e->cfg.n_envs) {
+    return fail(e, ARCLE_ERR_ARG, "arcle_place_rows: rows == NULL takes the resident envs (n_rows <= n_envs)");
+  }
+  DeviceGuard guard(e->device);
+  arcle::PlaceParams x = {};
+  x.p = e->base;
+  x.p.n_resident = x.p.n_envs;
+  x.p.n_envs = n_rows;
+  x.p.rows_in = rows;
+  x.p.rows_in_stride = rows ? stride : 0;
+  x.max_comp = max_comp;
+  x.max_dist = max_dist > 2 * ARCLE_MAX_CELLS ? 2 * ARCLE_MAX_CELLS : max_dist;  // (no translation is farther: the sums stay small)
+  x.count = count;
+  x.bits = bits;
+  x.src_env = src_env;
+  x.place = place;
+  x.base = base;
+  const dim3 g = grid_for(n_rows, COMP_WAVES_PER_WG), b(64 * COMP_WAVES_PER_WG);
+  if (width_class(e->base) != arcle::FW_GENERIC) hipLaunchKernelGGL(arcle_place_kernel<arcle::FW_FAST>, g, b, 0, (hipStream_t)stream, x);
+  else hipLaunchKernelGGL(arcle_place_kernel<arcle::FW_GENERIC>, g, b, 0, (hipStream_t)stream, x);
   HIP_TRY(e, hipGetLastError());
   return ARCLE_OK;
 }

@@ -726,6 +726,36 @@ class EnvBatch:
                                               self._stream()), "arcle_objects_rows")
         return out
 
+    def place_rows(self, rows, count, bits, src_env=None, max_dist=None, out=None):
+        """Where each object of every state row best fits the answer (arcle_place_rows): rows int8 [M, >= L] (any stride / alignment;
+        read only) or None = the resident envs; count int32 [M, 2] or None (every row has C objects) and bits uint8 [M, C, 128] as
+        `components_rows` / `objects_rows` return them; src_env int32 [M] = the env whose answer judges row m (None: env m); max_dist
+        None: no limit on |dx| + |dy|.  Returns (place int32 [M, C, 4] = dx, dy, correct at the best translation, correct at (0, 0),
+        base int32 [M, 2] = the dense pair of the row's own grid): the translation (dx rows down, dy columns right; the object's box
+        stays inside grid_dim) whose Move macro — select the object, Move |dx| + |dy| times — scores the most correct cells, ties to
+        the nearer one, then the smaller dx, then the smaller dy; entries k >= count are not written.  The definition:
+        include/arcle_hip.h; its NumPy mirror: arcle_amd.search.place_numpy.  out: the pair of a previous call with the same shapes
+        (captured graphs).  Nothing of the batch is touched."""
+        assert bits.dtype == torch.uint8 and bits.dim() == 3 and bits.shape[2] == _lib.BITS_STRIDE and bits.is_contiguous()
+        C = int(bits.shape[1])
+        if rows is None:
+            M, ptr, stride = int(bits.shape[0]), None, 0
+        else:
+            assert rows.dtype == torch.int8 and rows.dim() == 2 and rows.stride(1) == 1
+            M, ptr, stride = int(rows.shape[0]), _ptr(rows), rows.stride(0)
+        assert int(bits.shape[0]) == M
+        assert count is None or (count.dtype == torch.int32 and tuple(count.shape) == (M, 2) and count.is_contiguous())
+        assert src_env is None or (src_env.dtype == torch.int32 and tuple(src_env.shape) == (M,) and src_env.is_contiguous())
+        if out is None:
+            out = (torch.zeros((M, C, 4), dtype=torch.int32, device=self.device), torch.zeros((M, 2), dtype=torch.int32, device=self.device))
+        place, base = out
+        assert place.dtype == torch.int32 and tuple(place.shape) == (M, C, 4) and place.is_contiguous()
+        assert base is None or (base.dtype == torch.int32 and tuple(base.shape) == (M, 2) and base.is_contiguous())
+        D = 0x7fffffff if max_dist is None else int(max_dist)
+        self._check(self.L.arcle_place_rows(self._h, M, ptr, stride, C, _ptr(count), _ptr(bits), _ptr(src_env), D, _ptr(place), _ptr(base),
+                                            self._stream()), "arcle_place_rows")
+        return out
+
     def get_plane(self, name, out=None):
         """One key of the state dict as a dense [N, H, W] int8 array (device tensor, or a pinned host tensor passed as `out`):
         arcle_get_plane, a strided copy on the current stream."""

@@ -27,6 +27,9 @@ from ..engine import (AUG_PERMUTE, AUG_ROT90, EnvBatch, capture_guard, STEP_AUTO
 Components = collections.namedtuple("Components", "count left box seed color cells bits")
 # what ARCVecEnv.objects returns: a Components with the colour set of every object (the fields object_actions / object_macros read are the same)
 Objects = collections.namedtuple("Objects", "count left box seed color cells bits colors")
+# what ARCVecEnv.place returns: views of one int32 [M, C, 4] buffer (the best translation of every object, its correct cells, the
+# correct cells where it is) and the dense pair of every row's own grid
+Placements = collections.namedtuple("Placements", "dx dy correct stay base")
 
 
 def _table_of(env_cls, **ctor_kw):
@@ -670,6 +673,22 @@ class ARCVecEnv:
         a Components.  This env's state is not touched."""
         count, comp, mbits, cols = self.batch.objects_rows(rows, max_components, skip_color, any_color, diagonal, bits, colors)
         return Objects(count[:, 0], count[:, 1], comp[:, :, 0:4], comp[:, :, 4:6], comp[:, :, 6], comp[:, :, 7], mbits, cols)
+
+    def place(self, rows, objs, src_env=None, max_dist=None):
+        """Where each object best fits the answer (arcle_place_rows, one launch; no step is run): objs = a Components / Objects of
+        `rows` carrying `bits` (`components(bits=True)` / `objects(bits=True)`; rows None = this env's own states); src_env int32 [M] =
+        the env whose answer judges row m (None: env m); max_dist None: no limit on |dx| + |dy|.  Returns a Placements of device
+        tensors: dx, dy [M, C] = the translation (rows down, columns right; the object stays inside grid_dim) whose Move macro —
+        select the object, Move |dx| + |dy| times — leaves the most correct cells, ties to the nearer one; correct [M, C] = that
+        number, stay [M, C] = the number at (0, 0); base [M, 2] = the dense pair of the row's own grid.  Entries k >= count are zero.
+        `search.placement_macros` turns it into one macro per object.  This env's state is not touched."""
+        assert objs.bits is not None, "place needs the objects' bit rows (bits=True)"
+        M, C = int(objs.bits.shape[0]), int(objs.bits.shape[1])
+        count = torch.stack([objs.count, objs.left], 1).to(torch.int32).contiguous()
+        if src_env is not None:
+            src_env = src_env.to(device=self.device, dtype=torch.int32).contiguous()
+        place, base = self.batch.place_rows(rows, count, objs.bits.contiguous(), src_env, max_dist)
+        return Placements(place[:, :, 0], place[:, :, 1], place[:, :, 2], place[:, :, 3], base)
 
     def autotune(self, payload, operation=None, form="bbox"):
         """Times every launch plan the library has for this env's steps (self-ordering or not, the cache policies of the speculative grid

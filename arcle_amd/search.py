@@ -1,7 +1,9 @@
 """Search over ARCLE action sequences on top of `ARCVecEnv.expand`: the NumPy mirror of the device's state hash, a plain beam
 search, and the objects of a grid as candidate actions (`components_numpy`: the host mirror of arcle_components_rows;
 `object_actions` / `propose_objects`: its descriptors as a per-state action set for `beam_search(propose=...)` — the objects'
-bounding boxes, or with masks=True their exact cells as bit rows; `pack_bits` / `unpack_bits`: that layout in torch).
+bounding boxes, or with masks=True their exact cells as bit rows; `pack_bits` / `unpack_bits`: that layout in torch), and where each
+object best fits the answer (`place_numpy`: the host mirror of arcle_place_rows; `placement_macros` / `propose_placements`: the
+best translation of every object as ONE Move macro).
 
 The hash is defined in include/arcle_hip.h (next to arcle_hash_rows) and computed on the device by arcle_amd/csrc/arcle_search.h;
 `hash_rows_numpy` restates it on the host — the same arrangement as arcle_amd/sampling.py for the device RNG — and is what the tests
@@ -112,6 +114,8 @@ def beam_search(venv, rows, actions, width, depth, src_env=None, propose=None):
     depth for a candidate set PER STATE (`propose_objects`: the connected components of each state's grid); `actions` may then be
     None, and BeamResult.sequence is the list of the 5-tuples (x1, y1, x2, y2, op) themselves — BBoxWrapper actions; an index into
     a per-state set names nothing.  Slots with operation -1 are padding: their children carry a status bit and are dropped.
+    A propose that carries the attribute `wants_src = True` is called as `propose(venv, frontier_rows, src_env)`, src_env int32 [M] = the
+    env whose answer judges each frontier row (`propose_placements` looks at the answer); every other propose gets two arguments.
     A propose that returns {"bits": uint8 [M, K, 128], "operation": ...} (`propose_objects(masks=True)`: each object's exact cells)
     makes the sequence a list of (selection, op), selection a bool NumPy array [H, W] (H, W = venv.H, venv.W): what the reference's
     `step({"selection": selection, "operation": op})` takes.
@@ -150,7 +154,7 @@ def beam_search(venv, rows, actions, width, depth, src_env=None, propose=None):
         if M == 0:
             break
         if propose is not None:
-            cand = propose(venv, frontier)
+            cand = propose(venv, frontier, src) if getattr(propose, "wants_src", False) else propose(venv, frontier)
             form, pay = payload_of(cand)
             assert form != "point", "propose returns bbox or bits candidates"
             op = cand["operation"].to(device=dev, dtype=torch.int32).contiguous()
@@ -442,4 +446,108 @@ def propose_object_macros(box_ops, seed_ops, pair_ops, max_components=16, skip_c
             return object_macros(venv.objects(rows, max_components=max_components, skip_color=skip_color, any_color=any_color, diagonal=diagonal),
                                  box_ops, seed_ops, pair_ops)
         return object_macros(venv.components(rows, max_components=max_components, skip_color=skip_color), box_ops, seed_ops, pair_ops)
+    return propose
+
+
+# ---- where each object best fits the answer ----------------------------------------------------------------------------------------
+def place_numpy(grid, grid_dim, answer, answer_dim, masks, max_dist=None, full=False):
+    """The best translation of every object of ONE grid as arcle_place_rows reports it (include/arcle_hip.h) — the host mirror, straight
+    from the definition: every child grid is built and counted.  grid, answer int8 [H, W]; masks [n, H, W] (truthy = the object's
+    cells; cells outside grid_dim are ignored); max_dist None: no limit.  -> (place int32 [n, 4] = dx, dy, correct(best), correct(0, 0),
+    base (correct, total) of the grid itself); full=True adds table int32 [n, 2H - 1, 2W - 1]: correct(dx, dy) at [dx + H - 1,
+    dy + W - 1], -1 outside T.  The child of (dx, dy): the object's cells zeroed, then its POSITIVE cells pasted dx rows down and dy
+    columns right — what select + |dx| + |dy| Moves leave (object.py:60-138, 218-243); the candidates keep the object's box inside
+    grid_dim; ties go to the smaller |dx| + |dy|, then the smaller dx, then the smaller dy."""
+    grid, answer = np.asarray(grid).astype(np.int8), np.asarray(answer).astype(np.int8)
+    H, W = grid.shape
+    gh, gw = min(int(grid_dim[0]), H), min(int(grid_dim[1]), W)
+    ah, aw = min(int(answer_dim[0]), H), min(int(answer_dim[1]), W)
+    mh, mw = min(gh, ah), min(gw, aw)
+    D = 2 * (H + W) if max_dist is None else int(max_dist)
+    total = mh * mw + (abs(ah * aw - gh * gw) if (gh <= ah) == (gw <= aw) else abs(gh - ah) * mw + abs(gw - aw) * mh)
+    base = (int((grid[:mh, :mw] == answer[:mh, :mw]).sum()), total)
+    masks = np.asarray(masks).reshape(-1, H, W)
+    n = masks.shape[0]
+    place = np.zeros((n, 4), np.int32)
+    table = np.full((n, 2 * H - 1, 2 * W - 1), -1, np.int32)
+    for k in range(n):
+        B = np.zeros((H, W), bool)
+        B[:gh, :gw] = masks[k, :gh, :gw] != 0
+        back = np.where(B, 0, grid)
+        xs, ys = np.nonzero(B & (grid > 0))
+        cols = grid[xs, ys]
+        bx, by = np.nonzero(B)
+        x0, x1, y0, y1 = (bx.min(), bx.max(), by.min(), by.max()) if len(bx) else (0, gh - 1, 0, gw - 1)
+        best = None
+        for dx in range(max(-x0, -D), min(gh - 1 - x1, D) + 1) if len(bx) else (0,):
+            for dy in range(max(-y0, -D), min(gw - 1 - y1, D) + 1) if len(bx) else (0,):
+                if abs(dx) + abs(dy) > D:
+                    continue
+                child = back.copy()
+                child[xs + dx, ys + dy] = cols
+                c = int((child[:mh, :mw] == answer[:mh, :mw]).sum())
+                table[k, dx + H - 1, dy + W - 1] = c
+                key = (-c, abs(dx) + abs(dy), dx, dy)
+                if best is None or key < best:
+                    best = key
+        place[k] = (best[2], best[3], -best[0], table[k, H - 1, W - 1])
+    return (place, base, table) if full else (place, base)
+
+
+def placement_macros(objs, placements, move_ops, max_len):
+    """The best translation of every object (`ARCVecEnv.place` -> Placements) as ONE Move macro per object: {"bits": uint8 [M, C, T, 128],
+    "operation": int32 [M, C, T], "length": int32 [M, C]}, T = max_len.  Macro k is |dx| vertical Moves, then |dy| horizontal ones;
+    move_ops = (up, down, right, left) op indices — dx < 0 moves up, dy > 0 right (dirX / dirY of gen_move).  Step 0 carries the
+    object's bit row (objs.bits); every later step the zero mask, which continues the active object (object.py:102-107).  Slots with
+    k >= count, (dx, dy) == (0, 0), correct <= stay (the move gains nothing) or |dx| + |dy| > T get operation -1 at step 0 and length
+    1: one ARCLE_ST_BAD_OP child, dropped by beam_search.  Pure indexing on the device: no host synchronisation."""
+    assert objs.bits is not None, "placement_macros needs the objects' bit rows (bits=True)"
+    dev = objs.bits.device
+    M, C, S_ = (int(v) for v in objs.bits.shape)
+    T = int(max_len)
+    up, down, right, left = (int(o) for o in move_ops)
+    dx, dy = placements.dx.to(torch.int32), placements.dy.to(torch.int32)
+    nv, nh = dx.abs(), dy.abs()
+    there = torch.arange(C, device=dev).reshape(1, C) < objs.count.reshape(M, 1)
+    ok = there & ((nv + nh) > 0) & ((nv + nh) <= T) & (placements.correct > placements.stay)
+    t = torch.arange(T, device=dev, dtype=torch.int32).reshape(1, 1, T)
+    vert = torch.where(dx < 0, up, down).to(torch.int32).reshape(M, C, 1)
+    horiz = torch.where(dy > 0, right, left).to(torch.int32).reshape(M, C, 1)
+    minus = torch.full((), -1, dtype=torch.int32, device=dev)
+    op = torch.where(t < nv.reshape(M, C, 1), vert, torch.where(t < (nv + nh).reshape(M, C, 1), horiz, minus))
+    op = torch.where(ok.reshape(M, C, 1), op, minus)
+    length = torch.where(ok, nv + nh, torch.ones((), dtype=torch.int32, device=dev)).to(torch.int32)
+    bits = torch.zeros((M, C, T, S_), dtype=torch.uint8, device=dev)
+    bits[:, :, 0] = torch.where(ok.reshape(M, C, 1), objs.bits, torch.zeros((), dtype=torch.uint8, device=dev))
+    return {"bits": bits, "operation": op.to(torch.int32).contiguous(), "length": length.contiguous()}
+
+
+def propose_placements(move_ops, box_ops=(), seed_ops=(), max_dist=8, max_components=16, skip_color=0, any_color=False, diagonal=False):
+    """A `propose` for beam_search that answers "where does this object belong?": at every depth the objects of each frontier state's
+    grid (`venv.objects` / `venv.components` with their bit rows), first the singles of `object_actions(masks=True)` — box_ops on the
+    objects' exact cells, seed_ops on their seeds — as macros of length 1, then for every object ONE macro of up to max_dist Moves to
+    the translation at which it fits the answer best (`venv.place`, one launch; `placement_macros`), K = C * (len(box_ops) +
+    len(seed_ops) + 1), T = max(max_dist, 1).  move_ops = (up, down, right, left).  It looks at the answer of each row's env, so it
+    carries `wants_src = True` and beam_search calls it with (venv, rows, src_env)."""
+    move_ops, box_ops, seed_ops = tuple(int(o) for o in move_ops), list(box_ops), list(seed_ops)
+    T = max(int(max_dist), 1)
+
+    def propose(venv, rows, src_env=None):
+        if any_color or diagonal:
+            objs = venv.objects(rows, max_components=max_components, skip_color=skip_color, any_color=any_color, diagonal=diagonal, bits=True)
+        else:
+            objs = venv.components(rows, max_components=max_components, skip_color=skip_color, bits=True)
+        pm = placement_macros(objs, venv.place(rows, objs, src_env, max_dist), move_ops, T)
+        if not box_ops and not seed_ops:
+            return pm
+        single = object_actions(objs, box_ops, seed_ops, masks=True)
+        M, K1 = (int(v) for v in single["operation"].shape)
+        dev = single["bits"].device
+        b1 = torch.zeros((M, K1, T, int(single["bits"].shape[-1])), dtype=torch.uint8, device=dev)
+        b1[:, :, 0] = single["bits"]
+        o1 = torch.full((M, K1, T), -1, dtype=torch.int32, device=dev)
+        o1[:, :, 0] = single["operation"]
+        return {"bits": torch.cat([b1, pm["bits"]], 1).contiguous(), "operation": torch.cat([o1, pm["operation"]], 1).contiguous(),
+                "length": torch.cat([torch.ones((M, K1), dtype=torch.int32, device=dev), pm["length"]], 1).contiguous()}
+    propose.wants_src = True
     return propose

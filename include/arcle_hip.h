@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ARCLE_ABI_VERSION 11
+#define ARCLE_ABI_VERSION 12
 #define ARCLE_MAX_OPS 64
 #define ARCLE_MAX_CELLS 1024 /* H*W <= 1024: one 64-lane wavefront x 16 cells holds a plane (the one-wavefront-per-env kernels);
                                 larger planes (H, W <= 127) are served by the workgroup-per-env kernels — see "Grids beyond
@@ -541,6 +541,32 @@ int arcle_components_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, in
 #define ARCLE_OBJ_DIAG 2u
 int arcle_objects_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, int32_t skip_color,
                        uint32_t mode, int32_t* count, int32_t* comp, uint8_t* bits, uint32_t* colors, void* stream);
+/* Where each object of a state row best fits the answer (ABI 12): for object k of row m — a bit row of arcle_components_rows /
+ * arcle_objects_rows, taken as it stands — the translation whose Move macro (select the object, Move |dx| + |dy| times) leaves the
+ * most correct cells, and that number, in closed form: no step is run.
+ *   rows, stride  as for arcle_objects_rows (NULL: the resident envs 0 .. n_rows-1); only the grid and grid_dim are read
+ *   count         int32 [n_rows][2] as arcle_objects_rows writes it: objects k >= count[m][0] are neither read nor written (the value is
+ *                 clamped to [0, max_comp]); NULL: every row has max_comp objects
+ *   bits          uint8 [n_rows][max_comp][arcle_mask_bits_stride()], 2-byte aligned
+ *   src_env       int32 [n_rows]: the resident env whose answer plane and answer_dim judge row m, as arcle_expand_rows takes it (NULL:
+ *                 env m, then n_rows <= n_envs)
+ *   place         int32 [n_rows][max_comp][4] = dx, dy, correct(dx, dy), correct(0, 0)
+ *   base          optional int32 [n_rows][2]: the dense pair (correct, total) of the row's own grid
+ * With G the grid, (gh, gw) = min(grid_dim, (H, W)), A and (ah, aw) the answer of the env, B the cells of the bit row inside
+ * [0, gh) x [0, gw) (bits outside it or at indices >= H * W are ignored) and (x0, y0, x1, y1) B's inclusive box, the candidates are
+ *   T = {(dx, dy) : 0 <= x0 + dx, x1 + dx <= gh - 1, 0 <= y0 + dy, y1 + dy <= gw - 1, |dx| + |dy| <= max_dist}
+ * (dx along rows, BBoxWrapper's x; the object stays wholly inside grid_dim; (0, 0) is always in T; B empty: T = {(0, 0)}).  The child
+ * grid G'(dx, dy) at (x, y) is G[x - dx, y - dy] if that cell is in B and its byte, as int8, is > 0; else 0 if (x, y) is in B; else
+ * G[x, y] — what the Moves leave (object.py:60-138, 218-243) — and correct(dx, dy) counts the cells of [0, min(gh, ah)) x
+ * [0, min(gw, aw)) where G' equals A: the first number of the dense pair; the second does not change under a Move.  The best
+ * translation maximises correct; ties go to the smaller |dx| + |dy|, then the smaller dx, then the smaller dy.  Any large max_dist
+ * means no limit.  A row whose src_env names no env gets base = (0, 0) and place = (0, 0, 0, 0) for its objects.
+ * No side effects, as arcle_objects_rows; allocates nothing: may be captured.  One wavefront per row.  Refusals, nothing written:
+ * max_comp outside [1, ARCLE_MAX_CELLS], n_rows <= 0, a stride below the row length, bits or place NULL, an odd bits address,
+ * max_dist < 0, rows == NULL with n_rows > n_envs: ARCLE_ERR_ARG; more than ARCLE_MAX_CELLS cells per plane, or an env kind without
+ * an answer plane: ARCLE_ERR_CONFIG. */
+int arcle_place_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, const int32_t* count,
+                     const uint8_t* bits, const int32_t* src_env, int32_t max_dist, int32_t* place, int32_t* base, void* stream);
 /* One state plane as a dense [n_envs][H*W] int8 array (device or pinned host memory), a strided copy on the stream: the
  * get_state()/set_state() of single keys of the reference's state dict. */
 int arcle_get_plane(arcle_env* env, int plane, int8_t* dst, void* stream);
