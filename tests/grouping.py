@@ -228,8 +228,9 @@ def _tasks(rng, N, H, W):
 
 
 def _actions(rng, ops, ingress, N, research):
-    """One step's actions: a third object operations (every group trades), Submits, and — outside the research step, whose reference is
-    the same emulator anyway — op indices beyond the table: the 35-74 range of the adversarial GPU streams, 64 and more included."""
+    """One step's actions: a third object operations (every group trades), Submits, and — research=False; launch_errors passes that for
+    the research step too when it compares with the episode model — op indices beyond the table: the 35-74 range of the adversarial GPU
+    streams, 64 and more included."""
     n_ops = len(ops)
     op = rng.integers(0, n_ops, N).astype(np.int32)
     lng = rng.random(N) < 0.33
@@ -263,7 +264,8 @@ def launch_errors(row_name, ingress, n=512, steps=6, seed=0, wpw=4, step_limit=4
     """`steps` launches of the row's flag set: the plain twin (the same emulator stepping env i in slot i) against the self-ordering launch
     with its slots run ascending, descending and shuffled.  Compared bit-exact after every launch: reward, terminated, truncated, dense
     pairs, the rows, every byte of planes, records and counters, the sampler's side state, the status word.  oracle: the plain twin also
-    against OracleBackend.  The research step: step_limit 4 and counters drawn from 0..3; every group must hold an env at limit - 2 or
+    against OracleBackend — the research step against the episode model of tests/research_model.py (every output, field and the row),
+    and then with op indices beyond the table in its stream.  The research step: step_limit 4 and counters drawn from 0..3; every group must hold an env at limit - 2 or
     limit - 1 before every step (a condition on the inputs, read from the reference run — returned as an error if the draw misses it)."""
     row, flags, forms = LEAN_GROUPED[row_name]
     assert ingress in forms and grouped_applies(n)
@@ -296,8 +298,13 @@ def launch_errors(row_name, ingress, n=512, steps=6, seed=0, wpw=4, step_limit=4
             if flags & F.STEP_PACK_OBS:
                 be.set_packed_output()
         bes[name] = be
-    orc = None
-    if oracle:
+    orc = model = None
+    if oracle and research:
+        import research_model as M
+        model = M.ResearchModel(n, 30, 30, 2, ops, ins, outs, np.array([0, 2, 3, 7], np.int32), np.array([2, 1, 4, 2], np.int32), 0xABC0 + seed, 0,
+                                F.AUG_PERMUTE | F.AUG_ROT90, step_limit, flags)
+        model.orc.env.cnt[:, 0] = cnt0
+    elif oracle:
         orc = B.OracleBackend(n, 30, 30, 2, "o2arc", ops)
         orc.set_tasks(*tasks)
         orc.reset()
@@ -308,7 +315,7 @@ def launch_errors(row_name, ingress, n=512, steps=6, seed=0, wpw=4, step_limit=4
             near = ((c == step_limit - 2) | (c == step_limit - 1)).any(1)
             if not near.all():
                 errs.append(f"step {s}: groups {np.nonzero(~near)[0].tolist()} hold no env at limit - 2 or limit - 1: pick another seed")
-        pay, op, opay, oop = _actions(rng, ops, ingress, n, research)
+        pay, op, opay, oop = _actions(rng, ops, ingress, n, research and model is None)
         snaps = {}
         for name, be in bes.items():
             be.step(ingress, pay, op, flags)
@@ -323,6 +330,14 @@ def launch_errors(row_name, ingress, n=512, steps=6, seed=0, wpw=4, step_limit=4
                 if not np.array_equal(v, snaps[name][k]):
                     bad = np.nonzero((v != snaps[name][k]).reshape(len(v), -1).any(1))[0].tolist() if len(v) == n else []
                     errs.append(f"{row_name} {ingress} step {s} {name}: {k} differs from the plain launch (envs {bad[:8]})")
+        if model is not None:
+            want, be, tag = model.step("bbox", opay, oop), bes["plain"], f"{row_name} {ingress} step {s} against the model"
+            for name, got, exp in (("reward", be.reward, want["reward"]), ("terminated", be.term, want["terminated"]), ("truncated", be.trunc, want["truncated"]),
+                                   ("dense pair", be.dense, want["dense"]), ("filtered row", be.fused_flat(), model.rows(True))):
+                M._diff(errs, tag, name, got, exp, want["what"], oop)
+            M._state_diff(errs, tag, [(be, None)], model, want["what"], oop)
+            if want["status"] != int(snaps["plain"]["status"][0]):
+                errs.append(f"{tag}: status {int(snaps['plain']['status'][0])}, the oracle's {want['status']}")
         if orc is not None:
             r, t = orc.step("mask" if ingress in ("mask", "bits") else "bbox" if ingress == "bbox5" else ingress, opay, oop, flags)
             be = bes["plain"]

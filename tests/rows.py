@@ -7,6 +7,7 @@ import numpy as np
 
 import backends as B
 from oracle import oracle as O
+from research_model import dense_pair
 
 STEP_AUTORESET, STEP_ELIDE, STEP_TRUNCATE, STEP_DENSE, STEP_ROS, STEP_FLAT_OBS, STEP_ROWS_INC = 1, 2, 4, 16, 64, 128, 512
 
@@ -262,18 +263,14 @@ def dense_on_autoreset(cls, H=10, W=10):
             errs.append(f"step {s}: reward / terminated differ")
         d = be.dense
         skipped = ended | ((op >= 35) & ~ended)
-        gh, ah = orc.get("grid_dim").astype(int), orc.get("answer_dim").astype(int)
+        gd, ad = orc.get("grid_dim"), orc.get("answer_dim")
         g, a = orc.get("grid"), orc.get("answer")
         for n in range(N):
             if skipped[n]:
                 if tuple(d[n]) != (0, 0):
                     errs.append(f"step {s} env {n}: reset / skipped step reports dense {tuple(d[n])}, expected (0, 0)")
                 continue
-            mh, mw = min(gh[n, 0], ah[n, 0]), min(gh[n, 1], ah[n, 1])
-            correct = int((g[n, :mh, :mw] == a[n, :mh, :mw]).sum())
-            G, A = gh[n, 0] * gh[n, 1], ah[n, 0] * ah[n, 1]
-            total = mh * mw + (abs(A - G) if (gh[n, 0] <= ah[n, 0]) == (gh[n, 1] <= ah[n, 1]) else
-                               abs(gh[n, 0] - ah[n, 0]) * mw + abs(gh[n, 1] - ah[n, 1]) * mh)
+            correct, total, _ = dense_pair(g[n], gd[n], a[n], ad[n])  # (agents/env.py:44-58, written out in tests/research_model.py)
             if tuple(d[n]) != (correct, total):
                 errs.append(f"step {s} env {n}: dense {tuple(d[n])} != {(correct, total)}")
         ended = t2.astype(bool)

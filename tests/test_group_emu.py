@@ -81,6 +81,7 @@ CELLS = [(row, form) for row, (_, _, forms) in G.LEAN_GROUPED.items() for form i
 @pytest.mark.parametrize("row_name,ingress", CELLS, ids=[f"{r}-{f}" for r, f in CELLS])
 def test_whole_launches_under_every_slot_order(row_name, ingress):
     """n = 512 at 30 x 30 (two groups per XCD: the smallest launch), 6 steps, every cell of the LEAN table's grouped column.  The seed of the
-    research case is one for which every group holds an env at limit - 2 or limit - 1 before every step (launch_errors checks it)."""
-    errs = G.launch_errors(row_name, ingress, n=512, steps=6, seed=11, oracle=row_name == "hot")
+    research case is one for which every group holds an env at limit - 2 or limit - 1 before every step (launch_errors checks it).  The
+    plain launch is also compared with the oracle — the research row's with the episode model of tests/research_model.py."""
+    errs = G.launch_errors(row_name, ingress, n=512, steps=6, seed=11, oracle=row_name in ("hot", "research_inc"))
     assert not errs, "\n".join(errs[:12])
