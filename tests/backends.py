@@ -53,13 +53,20 @@ def checksum(a):
 BITS_STRIDE = 128
 
 
-def pack_bits(masks):
-    """[N,H,W] masks (truthy = non-zero) -> uint8 [N,128] rows, bit f of a row = cell f (the INGRESS_BITS form of include/arcle_hip.h)."""
+PLANE_SLACK = 1024  # readable bytes behind every plane (ARCLE_PLANE_SLACK, include/arcle_hip.h)
+SLACK_FILL = 0x55   # what fill_slack() writes there: a kernel that stores past the last env's row shows in slack_intact()
+
+
+def pack_bits(masks, stride=None):
+    """[N,H,W] masks (truthy = non-zero) -> uint8 [N,stride] rows, bit f of a row = cell f (the INGRESS_BITS form of include/arcle_hip.h).
+    stride: the handle's arcle_mask_bits_stride (a backend's `bits_stride`); None: that of a handle with the default plane stride."""
     m = np.asarray(masks)
     n = m.shape[0]
     flat = (m.reshape(n, -1) != 0)
     P = flat.shape[1]
-    out = np.zeros((n, BITS_STRIDE if P <= 1024 else ((P + 127) & ~127) // 8), np.uint8)  # (arcle_mask_bits_stride: plane stride / 8 beyond 1024 cells)
+    if stride is None:
+        stride = BITS_STRIDE if P <= 1024 else ((P + 127) & ~127) // 8  # (arcle_mask_bits_stride: plane stride / 8 beyond 1024 cells)
+    out = np.zeros((n, stride), np.uint8)
     pk = np.packbits(flat, axis=1, bitorder="little")
     out[:, :pk.shape[1]] = pk
     return out
@@ -175,7 +182,9 @@ class EmuBackend:
         self.P = H * W
         self.PS = self.PLANE_STRIDE or ((self.P + 127) & ~127)
         self.max_trial = max_trial
-        self.buf = {k: np.zeros((N, self.PS), np.int8) for k in O.KIND_PLANES[kind]}
+        # (PLANE_SLACK bytes behind every plane, as the library asks of its callers: the row kernels request 1024 bytes from an env's answer plane on)
+        self._store = {k: np.zeros(N * self.PS + PLANE_SLACK, np.int8) for k in O.KIND_PLANES[kind]}
+        self.buf = {k: v[:N * self.PS].reshape(N, self.PS) for k, v in self._store.items()}
         self.rec = np.zeros((N, 16), np.int8)
         self.cnt = np.zeros((N, 2), np.int32)
         self.reward = np.zeros(N, np.int32)
@@ -424,6 +433,23 @@ class EmuBackend:
     def padding_is_zero(self):
         return all(not b[:, self.P:].any() for b in self.buf.values())
 
+    bits_stride = BITS_STRIDE  # bytes between the envs' rows of a bit-packed mask array (arcle_mask_bits_stride)
+
+    def start_accounting(self):
+        self.acct[:] = 0
+
+    def accounting(self):
+        """(algorithmic bytes, issued bytes) over all envs since start_accounting()."""
+        return int(self.acct[:self.N].sum()), int(self.acct[self.N:].sum())
+
+    def fill_slack(self):
+        for v in self._store.values():
+            v[self.N * self.PS:] = SLACK_FILL
+
+    def slack_intact(self):
+        """The PLANE_SLACK bytes behind every plane still hold what fill_slack() wrote."""
+        return all((v[self.N * self.PS:] == SLACK_FILL).all() for v in self._store.values())
+
     def counters(self):
         return self.cnt.copy()
 
@@ -494,6 +520,14 @@ class BigEmuBackend(EmuBackend):
         if getattr(self, "count_bytes", False):
             p.acct = self.acct.ctypes.data  # uint32 [2][N]: bytes without the row padding / bytes issued
         return p
+
+    @property
+    def bits_stride(self):
+        return self.PS // 8
+
+    def start_accounting(self):
+        self.acct[:] = 0
+        self.count_bytes = True
 
     def set_dense_output(self):
         self.dense = np.full((self.N, 2), -7, np.int32)
@@ -679,13 +713,41 @@ class BigEmuFourBackend(BigEmuBackend):
 class HipBackend:
     name = "hip"
 
+    PLANE_STRIDE = None  # override, as EmuBackend's: passed on as EnvBatch(plane_stride=)
+
     def __init__(self, N, H, W, max_trial, kind, ops):
         import torch
         from arcle_amd.engine import EnvBatch
         self.torch = torch
         self.N, self.H, self.W, self.kind = N, H, W, kind
-        self.b = EnvBatch(N, H, W, max_trial, kind)
+        self.b = EnvBatch(N, H, W, max_trial, kind, plane_stride=self.PLANE_STRIDE)
+        self.P, self.PS = self.b.P, self.b.PS
         self.b.set_op_table(ops)
+
+    @property
+    def bits_stride(self):
+        return self.b.bits_stride
+
+    def start_accounting(self):
+        self.b.enable_accounting(True)
+        self.b.accounting_ex(clear=True)
+
+    def accounting(self):
+        """(algorithmic bytes, issued bytes) over all envs since start_accounting()."""
+        return tuple(self.b.accounting_ex(clear=True)[:2])
+
+    def speculates(self, form, flags):
+        """The step launch of this form and flag set requests the grid plane before it knows the op (arcle_launch_info: a stream policy)."""
+        return not self.b.big and self.b.launch_info(form, flags)["policy"] != ""
+
+    def fill_slack(self):
+        for v in self.b._plane_store.values():
+            v[self.N * self.PS:] = SLACK_FILL
+
+    def slack_intact(self):
+        """The PLANE_SLACK bytes behind every plane still hold what fill_slack() wrote."""
+        self.torch.cuda.synchronize()
+        return all(bool((v[self.N * self.PS:] == SLACK_FILL).all()) for v in self.b._plane_store.values())
 
     def set_tasks(self, inp, idim, ans, adim):
         self.b.set_tasks_padded(inp, idim, ans, adim)
@@ -836,6 +898,15 @@ class HipBackend:
 
     def status(self, clear=True):
         return self.b.status(clear)
+
+
+class HipBatchView(HipBackend):
+    """HipBackend's view of an EnvBatch made elsewhere (the batches of tests/components.py, objects.py and place.py)."""
+
+    def __init__(self, b):
+        import torch
+        self.torch, self.b = torch, b
+        self.N, self.H, self.W, self.kind, self.P, self.PS = b.N, b.H, b.W, b.kind, b.P, b.PS
 
 
 BACKENDS = {"oracle": OracleBackend, "emu": EmuBackend, "hip": HipBackend}
@@ -1021,7 +1092,7 @@ def random_trace_compare(backend_cls, kind, ops, H, W, N, S, seed, max_trial=-1,
         if new_forms and ing == "bbox":
             r1, t1 = be.step("bbox5", np.concatenate([pay, op[:, None]], 1), None, flags)
         elif new_forms and ing == "mask":
-            r1, t1 = be.step("bits", pack_bits(pay), op, flags)
+            r1, t1 = be.step("bits", pack_bits(pay, be.bits_stride), op, flags)
         else:
             r1, t1 = be.step(ing, pay, op, flags)
         if observer is not None:

@@ -118,18 +118,18 @@ def _augmented(a, k, perm):
     return np.rot90(lut[a.astype(np.uint8)].astype(np.int8), k)
 
 
-def aug_case(be_cls):
+def aug_case(be_cls, sizes=((40, 40), (34, 45))):
     """Task augmentation on the big path: explicit (rot90 count + colour permutation per env) and device-drawn (the function of (seed, global
     env id, episode) arcle_amd.sampling mirrors), on a square plane; on a non-square one an explicit quarter turn that does not fit is
     refused (AUG_DOMAIN, env untouched) and a drawn one is dropped (k & 2)."""
     from arcle_amd import sampling
-    for (H, W) in ((40, 40), (34, 45)):
+    for (H, W) in sizes:
         N, T = 6, 5
         rng = np.random.default_rng(H + W)
-        ins = [rng.integers(0, 10, (rng.integers(2, H + 1), rng.integers(2, W + 1))).astype(np.int8) for _ in range(T)]
-        outs = [rng.integers(0, 10, (rng.integers(2, H + 1), rng.integers(2, W + 1))).astype(np.int8) for _ in range(T)]
+        ins = [rng.integers(0, 10, (rng.integers(min(2, H), H + 1), rng.integers(min(2, W), W + 1))).astype(np.int8) for _ in range(T)]
+        outs = [rng.integers(0, 10, (rng.integers(min(2, H), H + 1), rng.integers(min(2, W), W + 1))).astype(np.int8) for _ in range(T)]
         if H != W:  # one entry that only fits unturned, one that fits both ways
-            ins[0], outs[0] = ins[0][:, :W][:H], np.zeros((3, W), np.int8) + 4
+            ins[0], outs[0] = ins[0][:, :W][:H], np.zeros((min(3, H), W), np.int8) + 4
             ins[1], outs[1] = ins[1][:H, :H][:20, :25], outs[1][:20, :30]
         fits = [a.shape[1] <= H and a.shape[0] <= W and b_.shape[1] <= H and b_.shape[0] <= W for a, b_ in zip(ins, outs)]
         be = be_cls(N, H, W, 3, "o2arc", O.o2arc_ops())

@@ -51,8 +51,41 @@ def sizes():
     return out
 
 
+_generated = {}
+
+
+def generated_cases(H, W):
+    """Cases of a size the fixture does not hold, in its format: 3- and 10-colour noise, a two-colour checkerboard (H * W one-cell
+    components), one colour all over, a grid_dim smaller than H x W with arbitrary bytes outside it.  `want` holds components_numpy's
+    descriptors (the reference of every comparison here, pinned on the fixture by tests/test_components_host.py), no label plane."""
+    if (H, W) not in _generated:
+        rng = np.random.default_rng(5000 + 131 * H + W)
+        out = []
+
+        def want(g, dim, skip):
+            n, _, comp, _ = S.components_numpy(g, dim, 1024, skip)
+            return comp[:n].astype(np.int32)
+
+        def add(name, g, dim=(H, W)):
+            g, dim = np.asarray(g).astype(np.int8), np.asarray(dim, np.int8)
+            out.append({"name": f"{H}x{W} gen {name}", "H": H, "W": W, "grid": g, "dim": dim,
+                        "want": {s: (want(g, dim, s), None) for s in SKIPS}})
+        add("noise3", rng.choice([0, 3, 5], (H, W)))
+        add("noise10", rng.integers(0, 10, (H, W)))
+        xx, yy = np.mgrid[0:H, 0:W]
+        add("checker35", np.where((xx + yy) % 2 == 0, 3, 5))
+        add("uniform3", np.full((H, W), 3))
+        g = rng.integers(-128, 128, (H, W)).astype(np.int8)
+        gh, gw = max(1, H - 2), max(1, W - 3)
+        g[:gh, :gw] = rng.choice([0, 3, 5], (gh, gw))
+        add(f"shrunk dim {gh}x{gw}", g, (gh, gw))
+        _generated[(H, W)] = out
+    return _generated[(H, W)]
+
+
 def cases_of(H, W):
-    return [c for c in fixture() if (c["H"], c["W"]) == (H, W)]
+    """The fixture's cases of the size; generated ones for a size it does not hold (tests/strides.py)."""
+    return [c for c in fixture() if (c["H"], c["W"]) == (H, W)] or generated_cases(H, W)
 
 
 _mirror = {}
@@ -120,6 +153,7 @@ def _outputs(M, C, bits):
 
 class EmuComponents:
     """The emulated kernel.  fw: -1 = the instantiation the library launches for the width, 0 = FW_GENERIC at any width."""
+    BACKEND = B.EmuBackend  # (tests/strides.py: a subclass of another plane stride)
     name = "emu"
 
     def __init__(self, fw=-1):
@@ -139,13 +173,13 @@ class EmuComponents:
         return out
 
     def rows(self, kind, H, W, rows, layout, C, skip, bits):
-        be = B.EmuBackend(2, H, W, 3, kind, OPS[kind]())
+        be = self.BACKEND(2, H, W, 3, kind, OPS[kind]())
         buf, offset, stride = place(rows, layout)
         return self._run(be, rows.shape[0], C, skip, bits, buf.ctypes.data + offset, stride)
 
     def resident(self, kind, H, W, rows, cases, C, skip, bits):
         M = len(cases)
-        be = B.EmuBackend(M, H, W, 3, kind, OPS[kind]())
+        be = self.BACKEND(M, H, W, 3, kind, OPS[kind]())
         for k in be.buf:
             be.buf[k][:] = 0x55
         be.rec[:] = 0x55
@@ -156,6 +190,7 @@ class EmuComponents:
 
 class HipComponents:
     """EnvBatch.components_rows on the device."""
+    PLANE_STRIDE = None  # override, as HipBackend's: passed on as EnvBatch(plane_stride=)
     name = "hip"
 
     def __init__(self):
@@ -167,7 +202,7 @@ class HipComponents:
         from arcle_amd.engine import EnvBatch
         key = (kind, H, W, N)
         if key not in self._b:
-            self._b[key] = EnvBatch(N, H, W, 3, kind)
+            self._b[key] = EnvBatch(N, H, W, 3, kind, plane_stride=self.PLANE_STRIDE)
             self._b[key].set_op_table(OPS[kind]())
         return self._b[key]
 

@@ -524,7 +524,7 @@ FIELDS = [f for f in O.PLANES[:-1]] + [f for f in O.REC if f != "answer_dim"]
 
 def _send(be, form, pay, op, flags):
     if form == "bits":
-        return be.step("bits", B.pack_bits(pay), op, flags)
+        return be.step("bits", B.pack_bits(pay, be.bits_stride), op, flags)
     if form == "bbox5":
         return be.step("bbox5", np.concatenate([pay, op[:, None]], 1), None, flags)
     return be.step(form, pay, op, flags)

@@ -163,6 +163,7 @@ def _outputs(M, C, bits, colors):
 
 class EmuObjects:
     """The emulated kernel.  fw: -1 = the instantiation the library launches for the width, 0 = FW_GENERIC at any width."""
+    BACKEND = B.EmuBackend  # (tests/strides.py: a subclass of another plane stride)
     name, limit = "emu", 40
 
     def __init__(self, fw=-1):
@@ -183,13 +184,13 @@ class EmuObjects:
         return out
 
     def rows(self, kind, H, W, rows, layout, C, skip, mode, bits, colors):
-        be = B.EmuBackend(2, H, W, 3, kind, CP.OPS[kind]())
+        be = self.BACKEND(2, H, W, 3, kind, CP.OPS[kind]())
         buf, offset, stride = CP.place(rows, layout)
         return self._run(be, rows.shape[0], C, skip, mode, bits, colors, buf.ctypes.data + offset, stride)
 
     def resident(self, kind, H, W, rows, cases, C, skip, mode, bits, colors):
         M = len(cases)
-        be = B.EmuBackend(M, H, W, 3, kind, CP.OPS[kind]())
+        be = self.BACKEND(M, H, W, 3, kind, CP.OPS[kind]())
         for k in be.buf:
             be.buf[k][:] = 0x55
         be.rec[:] = 0x55
@@ -200,6 +201,7 @@ class EmuObjects:
 
 class HipObjects:
     """EnvBatch.objects_rows on the device."""
+    PLANE_STRIDE = None  # override, as HipBackend's: passed on as EnvBatch(plane_stride=)
     name, limit = "hip", 1024
 
     def __init__(self):
@@ -211,7 +213,7 @@ class HipObjects:
         from arcle_amd.engine import EnvBatch
         key = (kind, H, W, N)
         if key not in self._b:
-            self._b[key] = EnvBatch(N, H, W, 3, kind)
+            self._b[key] = EnvBatch(N, H, W, 3, kind, plane_stride=self.PLANE_STRIDE)
             self._b[key].set_op_table(CP.OPS[kind]())
         return self._b[key]
 

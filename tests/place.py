@@ -188,6 +188,7 @@ def _guarded(shape, dtype=np.int32, guard=16):
 
 class EmuPlace:
     """The emulated kernel.  fw: -1 = the instantiation the library launches for the width, 0 = FW_GENERIC at any width."""
+    BACKEND = B.EmuBackend  # (tests/strides.py: a subclass of another plane stride)
     name = "emu"
 
     def __init__(self, fw=-1):
@@ -197,7 +198,7 @@ class EmuPlace:
         M = len(cases)
         resident = layout == "resident"
         N, ans, adim, src, bad = envs_for(cases, resident, with_src, rng)
-        be = B.EmuBackend(N, H, W, 3, kind, CP.OPS[kind]())
+        be = self.BACKEND(N, H, W, 3, kind, CP.OPS[kind]())
         for k in be.buf:
             be.buf[k][:] = 0x55
         be.rec[:] = 0x55
@@ -230,6 +231,7 @@ class EmuPlace:
 
 class HipPlace:
     """EnvBatch.place_rows on the device."""
+    PLANE_STRIDE = None  # override, as HipBackend's: passed on as EnvBatch(plane_stride=)
     name = "hip"
 
     def __init__(self):
@@ -241,7 +243,7 @@ class HipPlace:
         from arcle_amd.engine import EnvBatch
         key = (kind, H, W, N)
         if key not in self._b:
-            self._b[key] = EnvBatch(N, H, W, 3, kind)
+            self._b[key] = EnvBatch(N, H, W, 3, kind, plane_stride=self.PLANE_STRIDE)
             self._b[key].set_op_table(CP.OPS[kind]())
         return self._b[key]
 

@@ -372,7 +372,7 @@ FORMS = {"bbox": ("bbox", "bbox5"), "mask": ("mask", "bits"), "point": ("point",
 
 def _send(be, form, pay, op, flags):
     if form == "bits":
-        return be.step("bits", B.pack_bits(pay), op, flags)
+        return be.step("bits", B.pack_bits(pay, be.bits_stride), op, flags)
     if form == "bbox5":
         return be.step("bbox5", np.concatenate([pay, op[:, None]], 1), None, flags)
     return be.step(form, pay, op, flags)

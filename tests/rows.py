@@ -88,10 +88,10 @@ def new_ingress_forms(cls):
     return errs
 
 
-def mask_bits_packer(cls):
+def mask_bits_packer(cls, sizes=((30, 30), (7, 12), (32, 32), (5, 5))):
     """arcle_pack_mask_bits == np.packbits of (mask != 0), any int8 values, odd grid sizes."""
     errs = []
-    for H, W in ((30, 30), (7, 12), (32, 32), (5, 5)):
+    for H, W in sizes:
         rng = np.random.default_rng(H * 100 + W)
         N = 9
         be = cls(N, H, W, -1, "o2arc", O.o2arc_ops())
@@ -99,16 +99,16 @@ def mask_bits_packer(cls):
         m[0] = 0
         m[1] = 1
         got = be.pack_mask_bits(m)
-        if not np.array_equal(got, B.pack_bits(m)):
+        if not np.array_equal(got, B.pack_bits(m, be.bits_stride)):
             errs.append(f"{H}x{W}: packed bit rows differ")
     return errs
 
 
-def state_rows_roundtrip(cls):
+def state_rows_roundtrip(cls, cases=(("o2arc", 30, 30), ("o2arc", 7, 12), ("arc", 30, 30), ("raw", 5, 5))):
     """get_state_rows (the pinned flat writer) -> set_state_rows on a fresh batch reproduces every state field; masked ingest leaves
     the other envs alone; rows built on the host from the ORACLE's state ingest to the oracle's state."""
     errs = []
-    for kind, H, W in (("o2arc", 30, 30), ("o2arc", 7, 12), ("arc", 30, 30), ("raw", 5, 5)):
+    for kind, H, W in cases:
         N = 7
         be, orc, rng, ops = _pair(cls, N, H, W, seed=H + W, kind=kind, warm=14)
         rows = be.flat_obs(False)

@@ -15,6 +15,7 @@ from arcle_amd import search as S
 from oracle import oracle as O
 
 CASES = (("o2arc", 30, 30, 3), ("o2arc", 7, 12, -1), ("o2arc", 12, 12, 1), ("arc", 30, 30, 3), ("raw", 5, 5, 2))  # = rows.transition_rows
+FAST_CASES = (("o2arc", 20, 24, 3), ("o2arc", 16, 16, 3))  # the FW_FAST kernels below 1024 bytes: rows of 512 and 256 bytes, 32 and 16 live lanes
 ST_BAD_OP, ST_ROTATE_DOMAIN, ST_BAD_TASK = 1, 2, 4
 STEP_DENSE = 16
 EMU_DIR = os.path.join(B.ROOT, "tests", "emu")

@@ -63,7 +63,7 @@ def test_transition_rows_continue_the_object(case):
     assert not errs, "\n".join(errs[:10])
 
 
-@pytest.mark.parametrize("kind,H,W,mt", [c for c in SR.CASES if c[0] == "o2arc"] + [("o2arc", 32, 32, 3)])
+@pytest.mark.parametrize("kind,H,W,mt", [c for c in SR.CASES if c[0] == "o2arc"] + [("o2arc", 32, 32, 3)] + list(SR.FAST_CASES))
 def test_expand_rows_continue_the_parents_object(kind, H, W, mt):
     errs = D.expansion_check(SB.HipBitsBackend, kind, H, W, mt)
     assert not errs, "\n".join(errs[:10])

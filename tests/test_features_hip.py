@@ -195,65 +195,7 @@ def test_sharded_env_over_rccl_world_size_1():
 def test_raw_c_abi_as_integration_md():
     """Drives libarcle_hip.so exactly as INTEGRATION.md §2 does: no torch buffers — the library allocates the planes
     (bufs = NULL), arcle_get_buffers names them, plain hipMemcpy moves data, NULL stream."""
-    from arcle_amd import _lib
-    L = _lib.lib()
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    hip.hipFree.argtypes = [ctypes.c_void_p]
-    H2D, D2H = 1, 2
-    N, H, W = 96, 30, 30
-    cfg = _lib.Config(N, H, W, 3, -1, 0)
-    h = ctypes.c_void_p()
-    assert L.arcle_create(ctypes.byref(cfg), None, ctypes.byref(h)) == 0
-    bufs = _lib.Buffers()
-    assert L.arcle_get_buffers(h, ctypes.byref(bufs)) == 0
-    PS = 1024  # ARCLE_DEFAULT_PLANE_STRIDE(900)
-    ops = (ctypes.c_uint32 * 35)(*O.o2arc_ops())
-    assert L.arcle_set_op_table(h, ops, 35) == 0
-    rng = np.random.default_rng(9)
-    orc = B.OracleBackend(N, H, W, 3, "o2arc", O.o2arc_ops())
-    inp = np.zeros((N, H, W), np.int8)
-    dims = rng.integers(1, 31, (N, 2)).astype(np.int8)
-    for n in range(N):
-        inp[n, :dims[n, 0], :dims[n, 1]] = rng.integers(0, 10, (dims[n, 0], dims[n, 1]))
-    orc.set_tasks(inp, dims, inp, dims)
-    orc.reset()
-
-    def upload_plane(pl, arr):
-        rows = np.zeros((N, PS), np.int8)
-        rows[:, :H * W] = arr.reshape(N, -1)
-        assert hip.hipMemcpy(bufs.plane[pl], rows.ctypes.data, rows.nbytes, H2D) == 0
-    upload_plane(0, inp)
-    upload_plane(7, inp)
-    rec = np.zeros((N, 16), np.int8)
-    rec[:, 0:2], rec[:, 14:16] = dims, dims
-    assert hip.hipMemcpy(bufs.rec, rec.ctypes.data, rec.nbytes, H2D) == 0
-    assert L.arcle_reset(h, None, None) == 0
-    dev = {k: ctypes.c_void_p() for k in ("bbox", "op", "reward", "term")}
-    for k, nbytes in (("bbox", N * 16), ("op", N * 4), ("reward", N * 4), ("term", N)):
-        assert hip.hipMalloc(ctypes.byref(dev[k]), nbytes) == 0
-    for s in range(24):
-        bb = rng.integers(0, 30, (N, 4)).astype(np.int32)
-        op = rng.integers(0, 35, N).astype(np.int32)
-        hip.hipMemcpy(dev["bbox"], bb.ctypes.data, bb.nbytes, H2D)
-        hip.hipMemcpy(dev["op"], op.ctypes.data, op.nbytes, H2D)
-        assert L.arcle_step_bbox(h, dev["bbox"], dev["op"], dev["reward"], dev["term"], 0, None) == 0
-        reward, term = np.zeros(N, np.int32), np.zeros(N, np.uint8)
-        hip.hipMemcpy(reward.ctypes.data, dev["reward"], reward.nbytes, D2H)  # (synchronises the NULL stream)
-        hip.hipMemcpy(term.ctypes.data, dev["term"], term.nbytes, D2H)
-        r2, t2 = orc.step("bbox", bb, op)
-        assert np.array_equal(reward, r2) and np.array_equal(term, t2), s
-    for pl, name in ((1, "grid"), (2, "selected"), (3, "clip"), (4, "object"), (6, "background")):
-        rows = np.zeros((N, PS), np.int8)
-        hip.hipMemcpy(rows.ctypes.data, bufs.plane[pl], rows.nbytes, D2H)
-        assert np.array_equal(rows[:, :H * W].reshape(N, H, W), orc.get(name)), name
-        assert not rows[:, H * W:].any()
-    st = ctypes.c_uint32(0)
-    assert L.arcle_get_status(h, ctypes.byref(st), 1, None) == 0 and st.value == orc.status()
-    for k in dev.values():
-        hip.hipFree(k)
-    assert L.arcle_destroy(h) == 0
+    F.raw_c_abi(96, 30, 30)
 
 
 def test_device_cuda_means_the_current_device():

@@ -66,3 +66,10 @@ def test_sanitized_standalone_emulator(form):
         assert np.array_equal(got[..., 0].astype(np.int32), want["reward"]) and np.array_equal(got[..., 1], want["term"])
         assert np.array_equal(got[..., 2], want["status"]) and np.array_equal(got[..., 3:5], want["hash"])
         assert np.array_equal(got[..., 5:7].astype(np.int32), want["dense"])
+
+
+@pytest.mark.parametrize("case", SR.FAST_CASES, ids=lambda c: f"{c[0]}-{c[1]}x{c[2]}")
+def test_macro_expansion_at_the_fast_widths(case):
+    """20 x 24 and 16 x 16 at the default stride: the FW_FAST kernel with 32 and 16 live lanes"""
+    errs = MC.parity(MC.EmuMacroBackend, cases=(case,))
+    assert not errs, "\n".join(errs[:10])

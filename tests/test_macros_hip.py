@@ -178,3 +178,10 @@ def test_expand_macros_in_a_captured_graph():
         torch.cuda.synchronize()
         for a, b in zip(out, ref):
             assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("case", SR.FAST_CASES, ids=lambda c: f"{c[0]}-{c[1]}x{c[2]}")
+def test_macro_expansion_at_the_fast_widths_hip(case):
+    """20 x 24 and 16 x 16 at the default stride: the FW_FAST kernel with 32 and 16 live lanes"""
+    errs = MC.parity(MC.HipMacroBackend, cases=(case,))
+    assert not errs, "\n".join(errs[:10])

@@ -73,3 +73,9 @@ def test_sanitized_standalone_emulator():
         assert np.array_equal(got[..., 0].astype(np.int32), want["reward"]) and np.array_equal(got[..., 1], want["term"])
         assert np.array_equal(got[..., 2], want["status"]) and np.array_equal(got[..., 3:5], want["hash"])
         assert np.array_equal(got[..., 5:7].astype(np.int32), want["dense"])
+
+
+def test_bit_rows_at_the_fast_widths():
+    """20 x 24 and 16 x 16 at the default stride: the FW_FAST kernels with 32 and 16 live lanes"""
+    errs = SB.expansion(SB.EmuBitsBackend, cases=SR.FAST_CASES) + SB.transitions(SB.EmuBitsBackend, cases=SR.FAST_CASES)
+    assert not errs, "\n".join(errs[:10])

@@ -182,3 +182,9 @@ def test_beam_search_on_masks_solves_the_planted_tasks_like_the_stub():
                 assert oa == ob and sa.dtype == bool and np.array_equal(sa, sb), (n, oa, ob)
             assert SB.replay_masks_on_oracle(inputs[n], dims[n], answers[n], res.sequence) == 1, n
     venv.check_errors()
+
+
+def test_bit_rows_at_the_fast_widths_hip():
+    """20 x 24 and 16 x 16 at the default stride: the FW_FAST kernels with 32 and 16 live lanes"""
+    errs = SB.expansion(SB.HipBitsBackend, cases=SR.FAST_CASES) + SB.transitions(SB.HipBitsBackend, cases=SR.FAST_CASES)
+    assert not errs, "\n".join(errs[:10])

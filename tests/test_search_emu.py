@@ -87,3 +87,9 @@ def test_sanitized_standalone_emulator():
         assert np.array_equal(got[..., 0].astype(np.int32), want["reward"]) and np.array_equal(got[..., 1], want["term"])
         assert np.array_equal(got[..., 2], want["status"]) and np.array_equal(got[..., 3:5], want["hash"])
         assert np.array_equal(got[..., 5:7].astype(np.int32), want["dense"])
+
+
+def test_expansion_and_hash_at_the_fast_widths():
+    """20 x 24 and 16 x 16 at the default stride: the FW_FAST kernels with 32 and 16 live lanes"""
+    errs = SR.expansion(SR.EmuSearchBackend, cases=SR.FAST_CASES) + SR.hash_strides(SR.EmuSearchBackend, cases=SR.FAST_CASES)
+    assert not errs, "\n".join(errs[:10])

@@ -187,3 +187,9 @@ def test_beam_search_counts_equal_the_oracle_stub():
     for n in range(16):
         res = S.beam_search(stub, rows[n:n + 1], acts, width=4096, depth=3, src_env=torch.tensor([n]))
         assert res.counts == p["counts"][n], (n, res.counts, p["counts"][n])
+
+
+def test_expansion_and_hash_at_the_fast_widths_hip():
+    """20 x 24 and 16 x 16 at the default stride: the FW_FAST kernels with 32 and 16 live lanes"""
+    errs = SR.expansion(SR.HipSearchBackend, cases=SR.FAST_CASES) + SR.hash_strides(SR.HipSearchBackend, cases=SR.FAST_CASES)
+    assert not errs, "\n".join(errs[:10])
