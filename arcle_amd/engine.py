@@ -756,6 +756,37 @@ class EnvBatch:
                                             self._stream()), "arcle_place_rows")
         return out
 
+    def stamp_rows(self, rows, count, bits, src_env=None, max_dist=None, blank=True, out=None):
+        """Where a COPY of each object of every state row best fits the answer (arcle_stamp_rows): rows, count, bits, src_env and
+        max_dist as for `place_rows`; blank = what the Paste of the caller's op table does (True: it writes the clip's whole
+        rectangle, zeros included — paste_blank, both default tables; False: the clip's positive cells only).  Returns (stamp int32
+        [M, C, 4] = px, py, correct(px, py), the object's cells inside grid_dim, base int32 [M, 2] = the dense pair of the row's own
+        grid): the cell (px, py) inside grid_dim, within max_dist of the object's box corner (x0, y0), at which CopyO + Paste —
+        copy the object, paste with the clip's top-left corner there; the stamp may hang over the bottom and right edges — scores
+        the most correct cells, ties to the nearer one, then the smaller px - x0, then the smaller py - y0; entries k >= count are
+        not written; an empty bit row gives (0, 0, base correct, 0).  The definition: include/arcle_hip.h; its NumPy mirror:
+        arcle_amd.search.stamp_numpy.  out: the pair of a previous call with the same shapes (captured graphs).  Nothing of the
+        batch is touched."""
+        assert bits.dtype == torch.uint8 and bits.dim() == 3 and bits.shape[2] == _lib.BITS_STRIDE and bits.is_contiguous()
+        C = int(bits.shape[1])
+        if rows is None:
+            M, ptr, stride = int(bits.shape[0]), None, 0
+        else:
+            assert rows.dtype == torch.int8 and rows.dim() == 2 and rows.stride(1) == 1
+            M, ptr, stride = int(rows.shape[0]), _ptr(rows), rows.stride(0)
+        assert int(bits.shape[0]) == M
+        assert count is None or (count.dtype == torch.int32 and tuple(count.shape) == (M, 2) and count.is_contiguous())
+        assert src_env is None or (src_env.dtype == torch.int32 and tuple(src_env.shape) == (M,) and src_env.is_contiguous())
+        if out is None:
+            out = (torch.zeros((M, C, 4), dtype=torch.int32, device=self.device), torch.zeros((M, 2), dtype=torch.int32, device=self.device))
+        stamp, base = out
+        assert stamp.dtype == torch.int32 and tuple(stamp.shape) == (M, C, 4) and stamp.is_contiguous()
+        assert base is None or (base.dtype == torch.int32 and tuple(base.shape) == (M, 2) and base.is_contiguous())
+        D = 0x7fffffff if max_dist is None else int(max_dist)
+        self._check(self.L.arcle_stamp_rows(self._h, M, ptr, stride, C, _ptr(count), _ptr(bits), _ptr(src_env), D, int(bool(blank)),
+                                            _ptr(stamp), _ptr(base), self._stream()), "arcle_stamp_rows")
+        return out
+
     def get_plane(self, name, out=None):
         """One key of the state dict as a dense [N, H, W] int8 array (device tensor, or a pinned host tensor passed as `out`):
         arcle_get_plane, a strided copy on the current stream."""

@@ -30,6 +30,9 @@ Objects = collections.namedtuple("Objects", "count left box seed color cells bit
 # what ARCVecEnv.place returns: views of one int32 [M, C, 4] buffer (the best translation of every object, its correct cells, the
 # correct cells where it is) and the dense pair of every row's own grid
 Placements = collections.namedtuple("Placements", "dx dy correct stay base")
+# what ARCVecEnv.stamp returns: views of one int32 [M, C, 4] buffer (the best paste position of a copy of every object, its correct
+# cells, the object's cells) and the dense pair of every row's own grid
+Stamps = collections.namedtuple("Stamps", "px py correct cells base")
 
 
 def _table_of(env_cls, **ctor_kw):
@@ -689,6 +692,21 @@ class ARCVecEnv:
             src_env = src_env.to(device=self.device, dtype=torch.int32).contiguous()
         place, base = self.batch.place_rows(rows, count, objs.bits.contiguous(), src_env, max_dist)
         return Placements(place[:, :, 0], place[:, :, 1], place[:, :, 2], place[:, :, 3], base)
+
+    def stamp(self, rows, objs, src_env=None, max_dist=None, blank=True):
+        """Where a COPY of each object best fits the answer (arcle_stamp_rows, one launch; no step is run): objs, rows, src_env and
+        max_dist as for `place`; blank = what the Paste of this env's op table does (True, the default tables: the clip's whole
+        rectangle is written, zeros included; False: its positive cells only).  Returns a Stamps of device tensors: px, py [M, C] =
+        the cell inside grid_dim, within max_dist of the object's box corner, at which CopyO + Paste — copy the object, paste with
+        the clip's top-left corner there — leaves the most correct cells, ties to the nearer one; correct [M, C] = that number,
+        cells [M, C] = the object's cells inside grid_dim; base [M, 2] = the dense pair of the row's own grid.  Entries k >= count
+        are zero.  `search.stamp_macros` turns it into one two-step macro per object.  This env's state is not touched."""
+        assert objs.bits is not None, "stamp needs the objects' bit rows (bits=True)"
+        count = torch.stack([objs.count, objs.left], 1).to(torch.int32).contiguous()
+        if src_env is not None:
+            src_env = src_env.to(device=self.device, dtype=torch.int32).contiguous()
+        stamp, base = self.batch.stamp_rows(rows, count, objs.bits.contiguous(), src_env, max_dist, blank)
+        return Stamps(stamp[:, :, 0], stamp[:, :, 1], stamp[:, :, 2], stamp[:, :, 3], base)
 
     def autotune(self, payload, operation=None, form="bbox"):
         """Times every launch plan the library has for this env's steps (self-ordering or not, the cache policies of the speculative grid

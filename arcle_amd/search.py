@@ -3,7 +3,8 @@ search, and the objects of a grid as candidate actions (`components_numpy`: the 
 `object_actions` / `propose_objects`: its descriptors as a per-state action set for `beam_search(propose=...)` — the objects'
 bounding boxes, or with masks=True their exact cells as bit rows; `pack_bits` / `unpack_bits`: that layout in torch), and where each
 object best fits the answer (`place_numpy`: the host mirror of arcle_place_rows; `placement_macros` / `propose_placements`: the
-best translation of every object as ONE Move macro).
+best translation of every object as ONE Move macro), and where a COPY of each object best fits it (`stamp_numpy`: the host mirror of
+arcle_stamp_rows; `stamp_macros` / `propose_stamps`: the best paste position of every object as ONE CopyO + Paste macro).
 
 The hash is defined in include/arcle_hip.h (next to arcle_hash_rows) and computed on the device by arcle_amd/csrc/arcle_search.h;
 `hash_rows_numpy` restates it on the host — the same arrangement as arcle_amd/sampling.py for the device RNG — and is what the tests
@@ -549,5 +550,110 @@ def propose_placements(move_ops, box_ops=(), seed_ops=(), max_dist=8, max_compon
         o1[:, :, 0] = single["operation"]
         return {"bits": torch.cat([b1, pm["bits"]], 1).contiguous(), "operation": torch.cat([o1, pm["operation"]], 1).contiguous(),
                 "length": torch.cat([torch.ones((M, K1), dtype=torch.int32, device=dev), pm["length"]], 1).contiguous()}
+    propose.wants_src = True
+    return propose
+
+
+# ---- where a copy of each object best fits the answer ------------------------------------------------------------------------------
+def stamp_numpy(grid, grid_dim, answer, answer_dim, masks, max_dist=None, blank=True, full=False):
+    """The best paste position of a copy of every object of ONE grid as arcle_stamp_rows reports it (include/arcle_hip.h) — the host
+    mirror, straight from the definition: every child grid is built and counted.  grid, answer int8 [H, W]; masks [n, H, W] (truthy =
+    the object's cells; cells outside grid_dim are ignored); max_dist None: no limit; blank = what Paste does (True: the clip's whole
+    rectangle is written; False: its positive cells only).  -> (stamp int32 [n, 4] = px, py, correct(px, py), the cells of B, base
+    (correct, total) of the grid itself); full=True adds table int32 [n, H, W]: correct(px, py), -1 outside T.  The child of (px,
+    py): the clip — the object's box cut out of the grid, the box's cells outside the object as 0 (object.py:291-312) — written with
+    its top-left corner at (px, py), cut at the plane's H x W (object.py:340-341); the candidates are the cells of grid_dim within
+    max_dist of the box's corner (x0, y0); ties go to the smaller |dx| + |dy|, (dx, dy) = (px - x0, py - y0), then the smaller dx,
+    then the smaller dy.  An empty object: (0, 0, base correct, 0) and a table of -1."""
+    grid, answer = np.asarray(grid).astype(np.int8), np.asarray(answer).astype(np.int8)
+    H, W = grid.shape
+    gh, gw = min(int(grid_dim[0]), H), min(int(grid_dim[1]), W)
+    ah, aw = min(int(answer_dim[0]), H), min(int(answer_dim[1]), W)
+    mh, mw = min(gh, ah), min(gw, aw)
+    D = 2 * (H + W) if max_dist is None else int(max_dist)
+    total = mh * mw + (abs(ah * aw - gh * gw) if (gh <= ah) == (gw <= aw) else abs(gh - ah) * mw + abs(gw - aw) * mh)
+    base = (int((grid[:mh, :mw] == answer[:mh, :mw]).sum()), total)
+    masks = np.asarray(masks).reshape(-1, H, W)
+    n = masks.shape[0]
+    stamp = np.zeros((n, 4), np.int32)
+    table = np.full((n, H, W), -1, np.int32)
+    for k in range(n):
+        B = np.zeros((H, W), bool)
+        B[:gh, :gw] = masks[k, :gh, :gw] != 0
+        bx, by = np.nonzero(B)
+        if not len(bx):
+            stamp[k] = (0, 0, base[0], 0)
+            continue
+        x0, x1, y0, y1 = bx.min(), bx.max(), by.min(), by.max()
+        clip = np.where(B, grid, 0)[x0:x1 + 1, y0:y1 + 1]
+        best = None
+        for px in range(gh):
+            for py in range(gw):
+                if abs(px - x0) + abs(py - y0) > D:
+                    continue
+                child = grid.copy()
+                part = clip[:H - px, :W - py]
+                dst = child[px:px + part.shape[0], py:py + part.shape[1]]
+                dst[...] = part if blank else np.where(part > 0, part, dst)
+                c = int((child[:mh, :mw] == answer[:mh, :mw]).sum())
+                table[k, px, py] = c
+                key = (-c, abs(px - x0) + abs(py - y0), px - x0, py - y0)
+                if best is None or key < best:
+                    best = key
+        stamp[k] = (x0 + best[2], y0 + best[3], -best[0], len(bx))
+    return (stamp, base, table) if full else (stamp, base)
+
+
+def stamp_macros(objs, stamps, copy_op, paste_op, W):
+    """The best paste position of a copy of every object (`ARCVecEnv.stamp` -> Stamps) as ONE two-step macro per object: {"bits": uint8
+    [M, C, 2, 128], "operation": int32 [M, C, 2], "length": int32 [M, C]}.  Step 0 is the object's bit row (objs.bits) with copy_op
+    (CopyO), step 1 the one-bit row of cell (px, py) — bit px * W + py, W = the plane's width — with paste_op.  Slots with k >= count
+    or correct <= base[0] (the stamp gains nothing) get operation -1 at step 0 and length 1: one ARCLE_ST_BAD_OP child, dropped by
+    beam_search.  Pure indexing on the device: no host synchronisation."""
+    assert objs.bits is not None, "stamp_macros needs the objects' bit rows (bits=True)"
+    dev = objs.bits.device
+    M, C, S_ = (int(v) for v in objs.bits.shape)
+    there = torch.arange(C, device=dev).reshape(1, C) < objs.count.reshape(M, 1)
+    ok = there & (stamps.correct > stamps.base[:, 0].reshape(M, 1))
+    zero = torch.zeros((), dtype=torch.uint8, device=dev)
+    pair = torch.where(torch.arange(2, device=dev).reshape(1, 1, 2) == 0, int(copy_op), int(paste_op)).to(torch.int32)
+    op = torch.where(ok.reshape(M, C, 1), pair, torch.full((), -1, dtype=torch.int32, device=dev))
+    length = torch.where(ok, torch.full((), 2, dtype=torch.int32, device=dev), torch.ones((), dtype=torch.int32, device=dev))
+    cell = (stamps.px.to(torch.int64) * int(W) + stamps.py.to(torch.int64)).clamp(0, 8 * S_ - 1)
+    one = torch.zeros((M, C, S_), dtype=torch.uint8, device=dev)
+    one.scatter_(-1, (cell >> 3).reshape(M, C, 1), (torch.ones((), dtype=torch.int64, device=dev) << (cell & 7)).to(torch.uint8).reshape(M, C, 1))
+    bits = torch.stack([objs.bits, one], 2)
+    bits = torch.where(ok.reshape(M, C, 1, 1), bits, zero)
+    return {"bits": bits.contiguous(), "operation": op.to(torch.int32).contiguous(), "length": length.to(torch.int32).contiguous()}
+
+
+def propose_stamps(copy_op, paste_op, box_ops=(), seed_ops=(), max_dist=None, max_components=16, skip_color=0, any_color=False, diagonal=False,
+                   blank=True):
+    """A `propose` for beam_search that answers "where does a copy of this object belong?": at every depth the objects of each
+    frontier state's grid (`venv.objects` / `venv.components` with their bit rows), first the singles of `object_actions(masks=True)`
+    — box_ops on the objects' exact cells, seed_ops on their seeds — as macros of length 1, then for every object ONE macro of two
+    steps, copy_op on the object and paste_op at the cell where the copy fits the answer best (`venv.stamp`, one launch;
+    `stamp_macros`), K = C * (len(box_ops) + len(seed_ops) + 1), T = 2.  blank must say what paste_op does in the caller's table
+    (True: paste_blank, both default tables).  It looks at the answer of each row's env, so it carries `wants_src = True` and
+    beam_search calls it with (venv, rows, src_env)."""
+    copy_op, paste_op, box_ops, seed_ops = int(copy_op), int(paste_op), list(box_ops), list(seed_ops)
+
+    def propose(venv, rows, src_env=None):
+        if any_color or diagonal:
+            objs = venv.objects(rows, max_components=max_components, skip_color=skip_color, any_color=any_color, diagonal=diagonal, bits=True)
+        else:
+            objs = venv.components(rows, max_components=max_components, skip_color=skip_color, bits=True)
+        sm = stamp_macros(objs, venv.stamp(rows, objs, src_env, max_dist, blank), copy_op, paste_op, venv.W)
+        if not box_ops and not seed_ops:
+            return sm
+        single = object_actions(objs, box_ops, seed_ops, masks=True)
+        M, K1 = (int(v) for v in single["operation"].shape)
+        dev = single["bits"].device
+        b1 = torch.zeros((M, K1, 2, int(single["bits"].shape[-1])), dtype=torch.uint8, device=dev)
+        b1[:, :, 0] = single["bits"]
+        o1 = torch.full((M, K1, 2), -1, dtype=torch.int32, device=dev)
+        o1[:, :, 0] = single["operation"]
+        return {"bits": torch.cat([b1, sm["bits"]], 1).contiguous(), "operation": torch.cat([o1, sm["operation"]], 1).contiguous(),
+                "length": torch.cat([torch.ones((M, K1), dtype=torch.int32, device=dev), sm["length"]], 1).contiguous()}
     propose.wants_src = True
     return propose

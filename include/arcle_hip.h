@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ARCLE_ABI_VERSION 12
+#define ARCLE_ABI_VERSION 13
 #define ARCLE_MAX_OPS 64
 #define ARCLE_MAX_CELLS 1024 /* H*W <= 1024: one 64-lane wavefront x 16 cells holds a plane (the one-wavefront-per-env kernels);
                                 larger planes (H, W <= 127) are served by the workgroup-per-env kernels — see "Grids beyond
@@ -567,6 +567,31 @@ int arcle_objects_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32
  * an answer plane: ARCLE_ERR_CONFIG. */
 int arcle_place_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, const int32_t* count,
                      const uint8_t* bits, const int32_t* src_env, int32_t max_dist, int32_t* place, int32_t* base, void* stream);
+/* Where a COPY of each object of a state row best fits the answer (ABI 13): for object k of row m — a bit row as for arcle_place_rows —
+ * the cell (px, py) at which CopyO + Paste (copy the object; paste the clip with its top-left corner at the selected cell) leaves the
+ * most correct cells, and that number, in closed form: no step is run.
+ *   rows, stride, count, bits, src_env, base, max_dist   as for arcle_place_rows (any large max_dist means no limit)
+ *   blank         what the Paste of the caller's table does: 1 = it writes the clip's whole rectangle, zeros included (paste_blank, the
+ *                 default tables' Paste: descriptor arg byte 1); 0 = only the clip's cells that are > 0
+ *   stamp         int32 [n_rows][max_comp][4] = px, py, correct(px, py), the cells of B; entries k >= count are not written
+ * With G the grid, (gh, gw) = min(grid_dim, (H, W)), A and (ah, aw) the answer of env src_env[m], (mh, mw) = min((gh, gw), (ah, aw)),
+ * B the cells of the bit row inside [0, gh) x [0, gw) (bits outside it or at indices >= H * W are ignored), (x0, y0, x1, y1) B's
+ * inclusive box and h x w its size, the clip is C[i, j] = G[x0 + i, y0 + j] if that cell is in B, else 0 (object.py:291-312), and the
+ * candidates are
+ *   T = {(px, py) : 0 <= px < gh, 0 <= py < gw, |px - x0| + |py - y0| <= max_dist}
+ * — the top-left corner lies inside grid_dim; the stamp may hang over the bottom or the right edge and is then cut at the PLANE's
+ * H x W, not at grid_dim (object.py:340-341); it never hangs over the top or the left.  The child G'(px, py) equals G except on
+ * [px, min(px + h, H)) x [py, min(py + w, W)), where with blank = 1 G' = C[x - px, y - py], and with blank = 0 the same only where
+ * C[x - px, y - py] > 0 as int8.  correct(px, py) counts the cells of [0, mh) x [0, mw) where G' equals A.  The best candidate
+ * maximises correct; ties go to the smaller |dx| + |dy| with (dx, dy) = (px - x0, py - y0), then the smaller dx, then the smaller dy.
+ * With blank = 1, (x0, y0) is a real edit: it zeroes the box's cells that are not in B.  B empty: (0, 0, base correct, 0).  A row
+ * whose src_env names no env gets base = (0, 0) and stamp = (0, 0, 0, 0) for its objects.
+ * No side effects; allocates nothing: may be captured.  One wavefront per row.  Refusals, nothing written: those of arcle_place_rows,
+ * and blank outside {0, 1}: ARCLE_ERR_ARG; more than ARCLE_MAX_CELLS cells per plane, or an env kind without an answer plane:
+ * ARCLE_ERR_CONFIG. */
+int arcle_stamp_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, const int32_t* count,
+                     const uint8_t* bits, const int32_t* src_env, int32_t max_dist, int32_t blank, int32_t* stamp, int32_t* base,
+                     void* stream);
 /* One state plane as a dense [n_envs][H*W] int8 array (device or pinned host memory), a strided copy on the stream: the
  * get_state()/set_state() of single keys of the reference's state dict. */
 int arcle_get_plane(arcle_env* env, int plane, int8_t* dst, void* stream);
