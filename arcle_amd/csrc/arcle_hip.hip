@@ -218,6 +218,7 @@ ARCLE_DEV void touch_args(const void* a, const void* b) { asm volatile("" ::"s"(
 #include "arcle_objects.h"     // ... under the multi-colour / 8-connected notions of an object (arcle_objects_rows)
 #include "arcle_place.h"       // the translation at which each object best fits the answer (arcle_place_rows)
 #include "arcle_stamp.h"       // the cell at which a copy of each object best fits the answer (arcle_stamp_rows)
+#include "arcle_turn.h"        // the translation at which each object best fits the answer after a rotation or a flip (arcle_turn_rows)
 #include "arcle_big_params.h"  // grids beyond ARCLE_MAX_CELLS: one workgroup per env (arcle_big.hip)
 
 using arcle::StepParams;
@@ -532,6 +533,14 @@ __global__ __launch_bounds__(64 * COMP_WAVES_PER_WG) void arcle_stamp_kernel(con
   const int row = wave_of_launch(COMP_WAVES_PER_WG);
   if (row >= x.p.n_envs) return;
   arcle::wave_stamp_row<FW>(x, nullptr, nullptr, row, (int)(threadIdx.x & 63));
+}
+
+// arcle_turn_rows: likewise
+template <int FW>
+__global__ __launch_bounds__(64 * COMP_WAVES_PER_WG) void arcle_turn_kernel(const arcle::TurnParams x) {
+  const int row = wave_of_launch(COMP_WAVES_PER_WG);
+  if (row >= x.p.n_envs) return;
+  arcle::wave_turn_row<FW>(x, nullptr, nullptr, row, (int)(threadIdx.x & 63));
 }
 
 __global__ __launch_bounds__(64 * WAVES_PER_WG) void arcle_reset_kernel(const StepParams p) {
@@ -2326,6 +2335,46 @@ extern "C" int arcle_stamp_rows(arcle_env* e, int32_t n_rows, const int8_t* rows
   const dim3 g = grid_for(n_rows, COMP_WAVES_PER_WG), b(64 * COMP_WAVES_PER_WG);
   if (width_class(e->base) != arcle::FW_GENERIC) hipLaunchKernelGGL(arcle_stamp_kernel<arcle::FW_FAST>, g, b, 0, (hipStream_t)stream, x);
   else hipLaunchKernelGGL(arcle_stamp_kernel<arcle::FW_GENERIC>, g, b, 0, (hipStream_t)stream, x);
+  HIP_TRY(e, hipGetLastError());
+  return ARCLE_OK;
+}
+
+// the best translation of every object of every row after each turn asked for (arcle_turn.h): reads what arcle_place_rows reads,
+// writes the caller's arrays — nothing of the handle is written
+extern "C" int arcle_turn_rows(arcle_env* e, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, const int32_t* count,
+                               const uint8_t* bits, const int32_t* src_env, int32_t max_dist, uint32_t turns, int32_t* turn, int32_t* base,
+                               void* stream) {
+  if (!e || !bits || !turn) return ARCLE_ERR_ARG;
+  if (n_rows <= 0) return fail(e, ARCLE_ERR_ARG, "n_rows must be positive");
+  if (e->big) return fail(e, ARCLE_ERR_CONFIG, "arcle_turn_rows: handles of at most 1024 cells per plane (ARCLE_MAX_CELLS)");
+  if (!e->bufs.plane[ARCLE_PL_ANSWER]) return fail(e, ARCLE_ERR_CONFIG, "arcle_turn_rows needs the answer plane");
+  if (max_comp < 1 || max_comp > ARCLE_MAX_CELLS) return fail(e, ARCLE_ERR_ARG, "arcle_turn_rows: max_comp in [1, ARCLE_MAX_CELLS]");
+  if (max_dist < 0) return fail(e, ARCLE_ERR_ARG, "arcle_turn_rows: max_dist must not be negative");
+  if (turns == 0u || turns > 31u) return fail(e, ARCLE_ERR_ARG, "arcle_turn_rows: turns is a non-empty set of ARCLE_TURN_* bits");
+  if ((uintptr_t)bits & 1u) return fail(e, ARCLE_ERR_ARG, "arcle_turn_rows: bit rows must be 2-byte aligned");
+  if (rows) {
+    if (int rc = check_rows(e, rows, stride, 0)) return rc;
+  } else if (n_rows > e->cfg.n_envs) {
+    return fail(e, ARCLE_ERR_ARG, "arcle_turn_rows: rows == NULL takes the resident envs (n_rows <= n_envs)");
+  }
+  DeviceGuard guard(e->device);
+  arcle::TurnParams x = {};
+  x.p = e->base;
+  x.p.n_resident = x.p.n_envs;
+  x.p.n_envs = n_rows;
+  x.p.rows_in = rows;
+  x.p.rows_in_stride = rows ? stride : 0;
+  x.max_comp = max_comp;
+  x.max_dist = max_dist > 2 * ARCLE_MAX_CELLS ? 2 * ARCLE_MAX_CELLS : max_dist;  // (no candidate is farther: the sums stay small)
+  x.count = count;
+  x.bits = bits;
+  x.src_env = src_env;
+  x.turn = turn;
+  x.base = base;
+  x.turns = turns;
+  const dim3 g = grid_for(n_rows, COMP_WAVES_PER_WG), b(64 * COMP_WAVES_PER_WG);
+  if (width_class(e->base) != arcle::FW_GENERIC) hipLaunchKernelGGL(arcle_turn_kernel<arcle::FW_FAST>, g, b, 0, (hipStream_t)stream, x);
+  else hipLaunchKernelGGL(arcle_turn_kernel<arcle::FW_GENERIC>, g, b, 0, (hipStream_t)stream, x);
   HIP_TRY(e, hipGetLastError());
   return ARCLE_OK;
 }

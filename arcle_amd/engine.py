@@ -787,6 +787,36 @@ class EnvBatch:
                                             _ptr(stamp), _ptr(base), self._stream()), "arcle_stamp_rows")
         return out
 
+    def turn_rows(self, rows, count, bits, src_env=None, max_dist=None, turns=31, out=None):
+        """Where each object of every state row best fits the answer after a rotation or a flip (arcle_turn_rows): rows, count, bits,
+        src_env and max_dist as for `place_rows`; turns = the set of turns asked for (bit t = slot t: Rotate 90, 180, 270, Flip H,
+        Flip V; _lib.TURN_*).  Returns (turn int32 [M, C, 5, 4] = dx, dy, correct, valid per turn, base int32 [M, 2] = the dense
+        pair of the row's own grid): per turn the translation (dx rows down, dy columns right, counted from where the turn leaves
+        the freshly selected object; the turned tile stays inside grid_dim) at which select + turn + |dx| + |dy| Moves score the
+        most correct cells, ties to the nearer one, then the smaller dx, then the smaller dy; valid = 0 (and zeros) where the turned
+        tile fits nowhere within max_dist.  Slots of turns not asked for and entries k >= count are not written (zero in a fresh
+        output).  The definition: include/arcle_hip.h; its NumPy mirror: arcle_amd.search.turn_numpy.  out: the pair of a previous
+        call with the same shapes (captured graphs).  Nothing of the batch is touched."""
+        assert bits.dtype == torch.uint8 and bits.dim() == 3 and bits.shape[2] == _lib.BITS_STRIDE and bits.is_contiguous()
+        C = int(bits.shape[1])
+        if rows is None:
+            M, ptr, stride = int(bits.shape[0]), None, 0
+        else:
+            assert rows.dtype == torch.int8 and rows.dim() == 2 and rows.stride(1) == 1
+            M, ptr, stride = int(rows.shape[0]), _ptr(rows), rows.stride(0)
+        assert int(bits.shape[0]) == M
+        assert count is None or (count.dtype == torch.int32 and tuple(count.shape) == (M, 2) and count.is_contiguous())
+        assert src_env is None or (src_env.dtype == torch.int32 and tuple(src_env.shape) == (M,) and src_env.is_contiguous())
+        if out is None:
+            out = (torch.zeros((M, C, 5, 4), dtype=torch.int32, device=self.device), torch.zeros((M, 2), dtype=torch.int32, device=self.device))
+        turn, base = out
+        assert turn.dtype == torch.int32 and tuple(turn.shape) == (M, C, 5, 4) and turn.is_contiguous()
+        assert base is None or (base.dtype == torch.int32 and tuple(base.shape) == (M, 2) and base.is_contiguous())
+        D = 0x7fffffff if max_dist is None else int(max_dist)
+        self._check(self.L.arcle_turn_rows(self._h, M, ptr, stride, C, _ptr(count), _ptr(bits), _ptr(src_env), D, int(turns),
+                                           _ptr(turn), _ptr(base), self._stream()), "arcle_turn_rows")
+        return out
+
     def get_plane(self, name, out=None):
         """One key of the state dict as a dense [N, H, W] int8 array (device tensor, or a pinned host tensor passed as `out`):
         arcle_get_plane, a strided copy on the current stream."""

@@ -33,6 +33,9 @@ Placements = collections.namedtuple("Placements", "dx dy correct stay base")
 # what ARCVecEnv.stamp returns: views of one int32 [M, C, 4] buffer (the best paste position of a copy of every object, its correct
 # cells, the object's cells) and the dense pair of every row's own grid
 Stamps = collections.namedtuple("Stamps", "px py correct cells base")
+# what ARCVecEnv.turn returns: views of one int32 [M, C, 5, 4] buffer (per turn — Rotate 90, 180, 270, Flip H, Flip V — the best
+# translation of every object after it, its correct cells, whether the turn has a candidate) and the dense pair of every row's own grid
+Turns = collections.namedtuple("Turns", "dx dy correct valid base")
 
 
 def _table_of(env_cls, **ctor_kw):
@@ -707,6 +710,22 @@ class ARCVecEnv:
             src_env = src_env.to(device=self.device, dtype=torch.int32).contiguous()
         stamp, base = self.batch.stamp_rows(rows, count, objs.bits.contiguous(), src_env, max_dist, blank)
         return Stamps(stamp[:, :, 0], stamp[:, :, 1], stamp[:, :, 2], stamp[:, :, 3], base)
+
+    def turn(self, rows, objs, src_env=None, max_dist=8, turns=31):
+        """Where each object best fits the answer after a rotation or a flip (arcle_turn_rows, one launch; no step is run): objs,
+        rows and src_env as for `place`; max_dist = the Moves after the turn at most (None: no limit); turns = the set of turns asked
+        for, bit t = slot t: Rotate 90, 180, 270, Flip H, Flip V.  Returns a Turns of device tensors: dx, dy [M, C, 5] = per turn
+        the translation, counted from where the turn leaves the freshly selected object (the turned tile stays inside grid_dim), at
+        which select + turn + |dx| + |dy| Moves leave the most correct cells, ties to the nearer one; correct [M, C, 5] = that
+        number; valid [M, C, 5] = 1, or 0 where the turned tile fits nowhere within max_dist; base [M, 2] = the dense pair of the
+        row's own grid.  Slots of turns not asked for and entries k >= count are zero.  `search.turn_macros` turns it into one macro
+        per object.  This env's state is not touched."""
+        assert objs.bits is not None, "turn needs the objects' bit rows (bits=True)"
+        count = torch.stack([objs.count, objs.left], 1).to(torch.int32).contiguous()
+        if src_env is not None:
+            src_env = src_env.to(device=self.device, dtype=torch.int32).contiguous()
+        turn, base = self.batch.turn_rows(rows, count, objs.bits.contiguous(), src_env, max_dist, turns)
+        return Turns(turn[..., 0], turn[..., 1], turn[..., 2], turn[..., 3], base)
 
     def autotune(self, payload, operation=None, form="bbox"):
         """Times every launch plan the library has for this env's steps (self-ordering or not, the cache policies of the speculative grid

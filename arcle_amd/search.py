@@ -657,3 +657,144 @@ def propose_stamps(copy_op, paste_op, box_ops=(), seed_ops=(), max_dist=None, ma
                 "length": torch.cat([torch.ones((M, K1), dtype=torch.int32, device=dev), sm["length"]], 1).contiguous()}
     propose.wants_src = True
     return propose
+
+
+# ---- where each object best fits the answer after a rotation or a flip -------------------------------------------------------------
+TURN_ROT90, TURN_ROT180, TURN_ROT270, TURN_FLIP_H, TURN_FLIP_V = 1, 2, 4, 8, 16  # ARCLE_TURN_*: slot t of the output <-> bit t
+
+
+def _turned(tile, t):
+    return (np.rot90(tile, 1), np.rot90(tile, 2), np.rot90(tile, 3), np.fliplr(tile), np.flipud(tile))[t]
+
+
+def turn_numpy(grid, grid_dim, answer, answer_dim, masks, max_dist=None, turns=31, full=False):
+    """The best translation of every object of ONE grid after each of the five turns, as arcle_turn_rows reports it
+    (include/arcle_hip.h) — the host mirror, straight from the definition: every child grid is built with np.rot90 / np.fliplr /
+    np.flipud and counted.  grid, answer int8 [H, W]; masks [n, H, W] (truthy = the object's cells; cells outside grid_dim are
+    ignored); max_dist None: no limit; turns = the mask of the turns asked for (bit t = slot t: rot90, rot180, rot270, flip H, flip
+    V).  -> (turn int32 [n, 5, 4] = dx, dy, correct, valid — zeros in the slots not asked for —, base (correct, total) of the grid
+    itself); full=True adds table int32 [n, 5, 2H - 1, 2W - 1]: correct(t, dx, dy) at [dx + H - 1, dy + W - 1], -1 outside T_t.
+    The child of (t, dx, dy): the object's cells zeroed, then the POSITIVE cells of the turned h' x w' tile (the object's box, 0
+    outside the object) written with its corner at (nx + dx, ny + dy), (nx, ny) = the corner at which the turn leaves a freshly
+    selected object (object.py:186-207: the box's corner for rot180 and the flips, (floor((2 x0 + h - w) / 2), floor((2 y0 + w - h) /
+    2)) for the quarter turns) — what select + turn + |dx| + |dy| Moves leave; the candidates keep the turned tile inside grid_dim;
+    ties go to the smaller |dx| + |dy|, then the smaller dx, then the smaller dy.  No candidate: (0, 0, 0, 0); an empty object:
+    (0, 0, base correct, 1)."""
+    grid, answer = np.asarray(grid).astype(np.int8), np.asarray(answer).astype(np.int8)
+    H, W = grid.shape
+    gh, gw = min(int(grid_dim[0]), H), min(int(grid_dim[1]), W)
+    ah, aw = min(int(answer_dim[0]), H), min(int(answer_dim[1]), W)
+    mh, mw = min(gh, ah), min(gw, aw)
+    D = 2 * (H + W) if max_dist is None else int(max_dist)
+    total = mh * mw + (abs(ah * aw - gh * gw) if (gh <= ah) == (gw <= aw) else abs(gh - ah) * mw + abs(gw - aw) * mh)
+    base = (int((grid[:mh, :mw] == answer[:mh, :mw]).sum()), total)
+    masks = np.asarray(masks).reshape(-1, H, W)
+    n = masks.shape[0]
+    turn = np.zeros((n, 5, 4), np.int32)
+    table = np.full((n, 5, 2 * H - 1, 2 * W - 1), -1, np.int32)
+    for k in range(n):
+        B = np.zeros((H, W), bool)
+        B[:gh, :gw] = masks[k, :gh, :gw] != 0
+        bx, by = np.nonzero(B)
+        for t in range(5):
+            if not (int(turns) >> t) & 1:
+                continue
+            if not len(bx):
+                turn[k, t] = (0, 0, base[0], 1)
+                continue
+            x0, x1, y0, y1 = int(bx.min()), int(bx.max()), int(by.min()), int(by.max())
+            h, w = x1 - x0 + 1, y1 - y0 + 1
+            back = np.where(B, 0, grid)
+            tile = _turned(np.where(B, grid, 0)[x0:x1 + 1, y0:y1 + 1], t)
+            th, tw = tile.shape
+            nx, ny = ((2 * x0 + h - w) // 2, (2 * y0 + w - h) // 2) if t in (0, 2) else (x0, y0)
+            ti, tj = np.nonzero(tile > 0)
+            cols = tile[ti, tj]
+            best = None
+            for px in range(0, gh - th + 1):
+                for py in range(0, gw - tw + 1):
+                    dx, dy = px - nx, py - ny
+                    if abs(dx) + abs(dy) > D:
+                        continue
+                    child = back.copy()
+                    child[px + ti, py + tj] = cols
+                    c = int((child[:mh, :mw] == answer[:mh, :mw]).sum())
+                    table[k, t, dx + H - 1, dy + W - 1] = c
+                    key = (-c, abs(dx) + abs(dy), dx, dy)
+                    if best is None or key < best:
+                        best = key
+            if best is not None:
+                turn[k, t] = (best[2], best[3], -best[0], 1)
+    return (turn, base, table) if full else (turn, base)
+
+
+def turn_macros(objs, turns, turn_ops, move_ops, max_len):
+    """The best turn + translation of every object (`ARCVecEnv.turn` -> Turns) as ONE macro per object: {"bits": uint8 [M, C, T, 128],
+    "operation": int32 [M, C, T], "length": int32 [M, C]}, T = max_len.  turn_ops = the op indices of rot90, rot180, rot270, flip H,
+    flip V in the caller's table, -1 where it has none (O2ARCv2Env: (24, -1, 25, 26, 27)); move_ops = (up, down, right, left).  Per
+    object the best valid turn that has an op: more correct, then fewer steps, then the lower slot.  Step 0 is the object's bit row
+    (objs.bits) with the turn's op; then |dx| vertical and |dy| horizontal Moves on the zero mask, which continues the active object
+    (object.py:102-107), as `placement_macros` lays them out.  Slots with k >= count, no valid turn, correct <= base[0] (the turn gains
+    nothing) or 1 + |dx| + |dy| > T get operation -1 at step 0 and length 1: one ARCLE_ST_BAD_OP child, dropped by beam_search.  Pure
+    indexing on the device: no host synchronisation."""
+    assert objs.bits is not None, "turn_macros needs the objects' bit rows (bits=True)"
+    dev = objs.bits.device
+    M, C, S_ = (int(v) for v in objs.bits.shape)
+    T = int(max_len)
+    up, down, right, left = (int(o) for o in move_ops)
+    tops = torch.as_tensor([int(o) for o in turn_ops], dtype=torch.int32, device=dev).reshape(1, 1, 5)
+    steps = turns.dx.to(torch.int64).abs() + turns.dy.to(torch.int64).abs()
+    usable = (turns.valid != 0) & (tops >= 0)
+    score = turns.correct.to(torch.int64) * 4096 - steps * 8 - torch.arange(5, device=dev).reshape(1, 1, 5)
+    score = torch.where(usable, score, torch.full((), -1, dtype=torch.int64, device=dev))
+    pick = score.argmax(-1, keepdim=True)
+    dx, dy = turns.dx.gather(-1, pick).reshape(M, C).to(torch.int32), turns.dy.gather(-1, pick).reshape(M, C).to(torch.int32)
+    correct = turns.correct.gather(-1, pick).reshape(M, C)
+    top = tops.expand(M, C, 5).gather(-1, pick).reshape(M, C, 1)
+    nv, nh = dx.abs(), dy.abs()
+    there = torch.arange(C, device=dev).reshape(1, C) < objs.count.reshape(M, 1)
+    ok = there & usable.any(-1) & (correct > turns.base[:, 0].reshape(M, 1)) & ((1 + nv + nh) <= T)
+    t = torch.arange(T, device=dev, dtype=torch.int32).reshape(1, 1, T)
+    vert = torch.where(dx < 0, up, down).to(torch.int32).reshape(M, C, 1)
+    horiz = torch.where(dy > 0, right, left).to(torch.int32).reshape(M, C, 1)
+    minus = torch.full((), -1, dtype=torch.int32, device=dev)
+    op = torch.where(t == 0, top, torch.where(t <= nv.reshape(M, C, 1), vert, torch.where(t <= (nv + nh).reshape(M, C, 1), horiz, minus)))
+    op = torch.where(ok.reshape(M, C, 1), op, minus)
+    length = torch.where(ok, 1 + nv + nh, torch.ones((), dtype=torch.int32, device=dev)).to(torch.int32)
+    bits = torch.zeros((M, C, T, S_), dtype=torch.uint8, device=dev)
+    bits[:, :, 0] = torch.where(ok.reshape(M, C, 1), objs.bits, torch.zeros((), dtype=torch.uint8, device=dev))
+    return {"bits": bits, "operation": op.to(torch.int32).contiguous(), "length": length.contiguous()}
+
+
+def propose_turns(turn_ops, move_ops, box_ops=(), seed_ops=(), max_dist=8, max_components=16, skip_color=0, any_color=False, diagonal=False):
+    """A `propose` for beam_search that answers "where does this object belong once it is rotated or mirrored?": at every depth the
+    objects of each frontier state's grid (`venv.objects` / `venv.components` with their bit rows), first the singles of
+    `object_actions(masks=True)` — box_ops on the objects' exact cells, seed_ops on their seeds — as macros of length 1, then for every
+    object ONE macro: the turn and the up to max_dist Moves after it that fit the answer best (`venv.turn`, one launch; `turn_macros`),
+    K = C * (len(box_ops) + len(seed_ops) + 1), T = 1 + max_dist.  turn_ops = (rot90, rot180, rot270, flip H, flip V) op indices, -1
+    where the table has none: only the turns that have an op are asked for.  It looks at the answer of each row's env, so it carries
+    `wants_src = True` and beam_search calls it with (venv, rows, src_env)."""
+    turn_ops, move_ops, box_ops, seed_ops = tuple(int(o) for o in turn_ops), tuple(int(o) for o in move_ops), list(box_ops), list(seed_ops)
+    assert len(turn_ops) == 5 and any(o >= 0 for o in turn_ops), "turn_ops: five op indices, at least one of them >= 0"
+    T = 1 + int(max_dist)
+    want = sum(1 << t for t, o in enumerate(turn_ops) if o >= 0)
+
+    def propose(venv, rows, src_env=None):
+        if any_color or diagonal:
+            objs = venv.objects(rows, max_components=max_components, skip_color=skip_color, any_color=any_color, diagonal=diagonal, bits=True)
+        else:
+            objs = venv.components(rows, max_components=max_components, skip_color=skip_color, bits=True)
+        tm = turn_macros(objs, venv.turn(rows, objs, src_env, max_dist, want), turn_ops, move_ops, T)
+        if not box_ops and not seed_ops:
+            return tm
+        single = object_actions(objs, box_ops, seed_ops, masks=True)
+        M, K1 = (int(v) for v in single["operation"].shape)
+        dev = single["bits"].device
+        b1 = torch.zeros((M, K1, T, int(single["bits"].shape[-1])), dtype=torch.uint8, device=dev)
+        b1[:, :, 0] = single["bits"]
+        o1 = torch.full((M, K1, T), -1, dtype=torch.int32, device=dev)
+        o1[:, :, 0] = single["operation"]
+        return {"bits": torch.cat([b1, tm["bits"]], 1).contiguous(), "operation": torch.cat([o1, tm["operation"]], 1).contiguous(),
+                "length": torch.cat([torch.ones((M, K1), dtype=torch.int32, device=dev), tm["length"]], 1).contiguous()}
+    propose.wants_src = True
+    return propose

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ARCLE_ABI_VERSION 13
+#define ARCLE_ABI_VERSION 14
 #define ARCLE_MAX_OPS 64
 #define ARCLE_MAX_CELLS 1024 /* H*W <= 1024: one 64-lane wavefront x 16 cells holds a plane (the one-wavefront-per-env kernels);
                                 larger planes (H, W <= 127) are served by the workgroup-per-env kernels — see "Grids beyond
@@ -592,6 +592,40 @@ int arcle_place_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t
 int arcle_stamp_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, const int32_t* count,
                      const uint8_t* bits, const int32_t* src_env, int32_t max_dist, int32_t blank, int32_t* stamp, int32_t* base,
                      void* stream);
+/* Where each object of a state row best fits the answer AFTER A TURN (ABI 14): for object k of row m — a bit row as for
+ * arcle_place_rows — and each turn asked for, the translation at which select + turn + Moves (select the object with the turn's op, then
+ * Move |dx| + |dy| times) leaves the most correct cells, and that number, in closed form: no step is run.
+ *   rows, stride, count, bits, src_env, base, max_dist   as for arcle_place_rows (any large max_dist means no limit)
+ *   turns         the set of turns asked for, ARCLE_TURN_* bits
+ *   turn          int32 [n_rows][max_comp][5][4] = dx, dy, correct, valid; slot t is bit t of the masks below.  Slots of turns not in
+ *                 `turns`, and of objects k >= count, are not written
+ * G, (gh, gw), A, (ah, aw), (mh, mw), B and its inclusive box (x0, y0, x1, y1) of size h x w are as for arcle_place_rows.  O is the
+ * h x w tile: O[i, j] = G[x0 + i, y0 + j] if that cell is in B, else 0.  For turn t, O_t is np.rot90(O, k) for the rotations by 90 k
+ * degrees, np.fliplr(O) for FLIP_H and np.flipud(O) for FLIP_V; its size h' x w' is (w, h) for ROT90 / ROT270, else (h, w).  The corner
+ * at which the turn leaves a freshly selected object is (nx, ny): (x0, y0) for ROT180, FLIP_H and FLIP_V; (floor((2 x0 + h - w) / 2),
+ * floor((2 y0 + w - h) / 2)) for ROT90 / ROT270 (object.py:186-207 with rotation_parity = 0: both parity branches reduce to it).  The
+ * candidates are
+ *   T_t = {(dx, dy) : 0 <= nx + dx, nx + dx + h' <= gh, 0 <= ny + dy, ny + dy + w' <= gw, |dx| + |dy| <= max_dist}
+ * — the turned tile lies wholly inside grid_dim, |dx| + |dy| Moves after the turn.  T_t may be empty (h > gw; or the tile overhangs at
+ * (nx, ny) and max_dist is too small), and (0, 0) is in T_t only when the turn leaves the tile inside grid_dim.  The child G'(t, dx, dy)
+ * is the background — G with B's cells zeroed — with the cells of O_t whose byte, as int8, is > 0 written at (nx + dx + i, ny + dy + j):
+ * what select + turn + Moves leave (object.py:113-138, 167-279).  correct counts the cells of [0, mh) x [0, mw) where G' equals A; the
+ * total does not change.  Per turn the best candidate maximises correct; ties go to the smaller |dx| + |dy|, then the smaller dx, then
+ * the smaller dy (arcle_place_rows' rule); valid = 1.  T_t empty: the slot is (0, 0, 0, 0).  B empty: (0, 0, base correct, 1) for every
+ * turn asked for.  A row whose src_env names no env gets base = (0, 0) and zeros.
+ * The diagonal flips (D0 / D1) are out of scope: the reference leaves object_dim untransposed for them (object.py:270-273), so their
+ * child is a truncated tile, not a turn of the object.
+ * No side effects; allocates nothing: may be captured.  One wavefront per row.  Refusals, nothing written: those of arcle_place_rows,
+ * and turns == 0 or a bit above ARCLE_TURN_FLIP_V: ARCLE_ERR_ARG; more than ARCLE_MAX_CELLS cells per plane, or an env kind without an
+ * answer plane: ARCLE_ERR_CONFIG. */
+#define ARCLE_TURN_ROT90 1u   /* gen_rotate(1) */
+#define ARCLE_TURN_ROT180 2u  /* gen_rotate(2) */
+#define ARCLE_TURN_ROT270 4u  /* gen_rotate(3) */
+#define ARCLE_TURN_FLIP_H 8u  /* gen_flip("H") */
+#define ARCLE_TURN_FLIP_V 16u /* gen_flip("V") */
+int arcle_turn_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, const int32_t* count,
+                    const uint8_t* bits, const int32_t* src_env, int32_t max_dist, uint32_t turns, int32_t* turn, int32_t* base,
+                    void* stream);
 /* One state plane as a dense [n_envs][H*W] int8 array (device or pinned host memory), a strided copy on the stream: the
  * get_state()/set_state() of single keys of the reference's state dict. */
 int arcle_get_plane(arcle_env* env, int plane, int8_t* dst, void* stream);
