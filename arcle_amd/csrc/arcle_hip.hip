@@ -219,6 +219,7 @@ ARCLE_DEV void touch_args(const void* a, const void* b) { asm volatile("" ::"s"(
 #include "arcle_place.h"       // the translation at which each object best fits the answer (arcle_place_rows)
 #include "arcle_stamp.h"       // the cell at which a copy of each object best fits the answer (arcle_stamp_rows)
 #include "arcle_turn.h"        // the translation at which each object best fits the answer after a rotation or a flip (arcle_turn_rows)
+#include "arcle_align.h"       // the offset at which the grid or the input best fits the answer's canvas (arcle_align_rows)
 #include "arcle_big_params.h"  // grids beyond ARCLE_MAX_CELLS: one workgroup per env (arcle_big.hip)
 
 using arcle::StepParams;
@@ -541,6 +542,14 @@ __global__ __launch_bounds__(64 * COMP_WAVES_PER_WG) void arcle_turn_kernel(cons
   const int row = wave_of_launch(COMP_WAVES_PER_WG);
   if (row >= x.p.n_envs) return;
   arcle::wave_turn_row<FW>(x, nullptr, nullptr, row, (int)(threadIdx.x & 63));
+}
+
+// arcle_align_rows: likewise
+template <int FW>
+__global__ __launch_bounds__(64 * COMP_WAVES_PER_WG) void arcle_align_kernel(const arcle::AlignParams x) {
+  const int row = wave_of_launch(COMP_WAVES_PER_WG);
+  if (row >= x.p.n_envs) return;
+  arcle::wave_align_row<FW>(x, nullptr, nullptr, row, (int)(threadIdx.x & 63));
 }
 
 __global__ __launch_bounds__(64 * WAVES_PER_WG) void arcle_reset_kernel(const StepParams p) {
@@ -2375,6 +2384,42 @@ extern "C" int arcle_turn_rows(arcle_env* e, int32_t n_rows, const int8_t* rows,
   const dim3 g = grid_for(n_rows, COMP_WAVES_PER_WG), b(64 * COMP_WAVES_PER_WG);
   if (width_class(e->base) != arcle::FW_GENERIC) hipLaunchKernelGGL(arcle_turn_kernel<arcle::FW_FAST>, g, b, 0, (hipStream_t)stream, x);
   else hipLaunchKernelGGL(arcle_turn_kernel<arcle::FW_GENERIC>, g, b, 0, (hipStream_t)stream, x);
+  HIP_TRY(e, hipGetLastError());
+  return ARCLE_OK;
+}
+
+// the best offset of the grid and / or the input of every row on the answer's canvas (arcle_align.h): reads the rows' grid and input
+// (or the resident planes), the answer plane and the records, writes the caller's arrays — nothing of the handle is written
+extern "C" int arcle_align_rows(arcle_env* e, int32_t n_rows, const int8_t* rows, int32_t stride, const int32_t* src_env, int32_t max_dist,
+                                uint32_t sources, int32_t blank, int32_t* align, int32_t* base, void* stream) {
+  if (!e || !align) return ARCLE_ERR_ARG;
+  if (n_rows <= 0) return fail(e, ARCLE_ERR_ARG, "n_rows must be positive");
+  if (e->big) return fail(e, ARCLE_ERR_CONFIG, "arcle_align_rows: handles of at most 1024 cells per plane (ARCLE_MAX_CELLS)");
+  if (!e->bufs.plane[ARCLE_PL_ANSWER]) return fail(e, ARCLE_ERR_CONFIG, "arcle_align_rows needs the answer plane");
+  if (max_dist < 0) return fail(e, ARCLE_ERR_ARG, "arcle_align_rows: max_dist must not be negative");
+  if (sources == 0u || sources > (ARCLE_ALIGN_GRID | ARCLE_ALIGN_INPUT)) return fail(e, ARCLE_ERR_ARG, "arcle_align_rows: sources is a non-empty set of ARCLE_ALIGN_* bits");
+  if (blank != 0 && blank != 1) return fail(e, ARCLE_ERR_ARG, "arcle_align_rows: blank is 0 or 1");
+  if (rows) {
+    if (int rc = check_rows(e, rows, stride, 0)) return rc;
+  } else if (n_rows > e->cfg.n_envs) {  // (with or without src_env: row m's grid is env m's)
+    return fail(e, ARCLE_ERR_ARG, "arcle_align_rows: rows == NULL takes the resident envs (n_rows <= n_envs)");
+  }
+  DeviceGuard guard(e->device);
+  arcle::AlignParams x = {};
+  x.p = e->base;
+  x.p.n_resident = x.p.n_envs;
+  x.p.n_envs = n_rows;
+  x.p.rows_in = rows;
+  x.p.rows_in_stride = rows ? stride : 0;
+  x.max_dist = max_dist > 2 * ARCLE_MAX_CELLS ? 2 * ARCLE_MAX_CELLS : max_dist;  // (no candidate is farther: the sums stay small)
+  x.sources = sources;
+  x.src_env = src_env;
+  x.align = align;
+  x.base = base;
+  x.blank = blank;
+  const dim3 g = grid_for(n_rows, COMP_WAVES_PER_WG), b(64 * COMP_WAVES_PER_WG);
+  if (width_class(e->base) != arcle::FW_GENERIC) hipLaunchKernelGGL(arcle_align_kernel<arcle::FW_FAST>, g, b, 0, (hipStream_t)stream, x);
+  else hipLaunchKernelGGL(arcle_align_kernel<arcle::FW_GENERIC>, g, b, 0, (hipStream_t)stream, x);
   HIP_TRY(e, hipGetLastError());
   return ARCLE_OK;
 }

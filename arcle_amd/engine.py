@@ -817,6 +817,34 @@ class EnvBatch:
                                            _ptr(turn), _ptr(base), self._stream()), "arcle_turn_rows")
         return out
 
+    def align_rows(self, rows=None, src_env=None, max_dist=None, sources=3, blank=True, out=None):
+        """The offset at which the grid or the input of every state row best fits the answer's canvas (arcle_align_rows): rows int8
+        [M, >= L] state rows (None: the resident envs, M = N, or the length of src_env / of `out`), src_env and max_dist as for
+        `place_rows`; sources = the set of sources asked for (_lib.ALIGN_GRID: slot 0, the row's grid; _lib.ALIGN_INPUT: slot 1, the
+        row's input); blank = what the caller's Paste does (True: paste_blank).  Returns (align int32 [M, 2, 8] = ox, oy, correct,
+        total, sh, sw, ah, aw per source, base int32 [M, 2] = the dense pair of the row's own grid): the offset at which [Copy of the
+        source's rectangle the canvas covers, resize_grid to answer_dim, Paste] leaves the most correct cells, ties to the nearer
+        one, then the smaller ox, then the smaller oy; total = ah * aw, the child's dense total; an all-zero (ox, oy, correct,
+        total) where a dim is 0.  Slots of sources not asked for are not written (zero in a fresh output).  The definition:
+        include/arcle_hip.h; its NumPy mirror: arcle_amd.search.align_numpy.  out: the pair of a previous call with the same shapes
+        (captured graphs).  Nothing of the batch is touched."""
+        if rows is None:
+            M = int(out[0].shape[0]) if out is not None else int(src_env.shape[0]) if src_env is not None else self.N
+            ptr, stride = None, 0
+        else:
+            assert rows.dtype == torch.int8 and rows.dim() == 2 and rows.stride(1) == 1
+            M, ptr, stride = int(rows.shape[0]), _ptr(rows), rows.stride(0)
+        assert src_env is None or (src_env.dtype == torch.int32 and tuple(src_env.shape) == (M,) and src_env.is_contiguous())
+        if out is None:
+            out = (torch.zeros((M, 2, 8), dtype=torch.int32, device=self.device), torch.zeros((M, 2), dtype=torch.int32, device=self.device))
+        align, base = out
+        assert align.dtype == torch.int32 and tuple(align.shape) == (M, 2, 8) and align.is_contiguous()
+        assert base is None or (base.dtype == torch.int32 and tuple(base.shape) == (M, 2) and base.is_contiguous())
+        D = 0x7fffffff if max_dist is None else int(max_dist)
+        self._check(self.L.arcle_align_rows(self._h, M, ptr, stride, _ptr(src_env), D, int(sources), int(blank), _ptr(align), _ptr(base),
+                                            self._stream()), "arcle_align_rows")
+        return out
+
     def get_plane(self, name, out=None):
         """One key of the state dict as a dense [N, H, W] int8 array (device tensor, or a pinned host tensor passed as `out`):
         arcle_get_plane, a strided copy on the current stream."""

@@ -36,6 +36,10 @@ Stamps = collections.namedtuple("Stamps", "px py correct cells base")
 # what ARCVecEnv.turn returns: views of one int32 [M, C, 5, 4] buffer (per turn — Rotate 90, 180, 270, Flip H, Flip V — the best
 # translation of every object after it, its correct cells, whether the turn has a candidate) and the dense pair of every row's own grid
 Turns = collections.namedtuple("Turns", "dx dy correct valid base")
+# what ARCVecEnv.align returns: views of one int32 [M, 2, 8] buffer (per source — the row's grid, the row's input — the best offset of
+# the source on the answer's canvas, its correct cells, the child's total, the source's and the answer's dims) and the dense pair of
+# every row's own grid
+Alignments = collections.namedtuple("Alignments", "ox oy correct total src_dim ans_dim base")
 
 
 def _table_of(env_cls, **ctor_kw):
@@ -726,6 +730,21 @@ class ARCVecEnv:
             src_env = src_env.to(device=self.device, dtype=torch.int32).contiguous()
         turn, base = self.batch.turn_rows(rows, count, objs.bits.contiguous(), src_env, max_dist, turns)
         return Turns(turn[..., 0], turn[..., 1], turn[..., 2], turn[..., 3], base)
+
+    def align(self, rows, src_env=None, max_dist=None, sources=3, blank=True):
+        """The offset at which the grid or the input of every state row best fits the answer's canvas (arcle_align_rows, one launch;
+        no step is run): rows and src_env as for `place`; max_dist = |ox| + |oy| at most (None: no limit); sources = the set of
+        sources asked for, bit 0 = slot 0 = the row's grid (Copy_O), bit 1 = slot 1 = the row's input (Copy_I); blank = what the
+        table's Paste does (True: paste_blank, both default tables).  Returns an Alignments of device tensors: ox, oy [M, 2] = per
+        source the offset at which [Copy of the source's rectangle the canvas covers, resize_grid to answer_dim, Paste] leaves the
+        most correct cells — canvas cell (i, j) takes source cell (i + ox, j + oy) — ties to the nearer one; correct [M, 2] = that
+        number; total [M, 2] = ah * aw, the child's dense total (0: no candidate); src_dim, ans_dim [M, 2, 2] = the source's and the
+        answer's dims; base [M, 2] = the dense pair of the row's own grid.  Slots of sources not asked for are zero.
+        `search.align_macros` turns it into one three-step macro per source.  This env's state is not touched."""
+        if src_env is not None:
+            src_env = src_env.to(device=self.device, dtype=torch.int32).contiguous()
+        al, base = self.batch.align_rows(rows, src_env, max_dist, sources, blank)
+        return Alignments(al[..., 0], al[..., 1], al[..., 2], al[..., 3], al[..., 4:6], al[..., 6:8], base)
 
     def autotune(self, payload, operation=None, form="bbox"):
         """Times every launch plan the library has for this env's steps (self-ordering or not, the cache policies of the speculative grid

@@ -798,3 +798,127 @@ def propose_turns(turn_ops, move_ops, box_ops=(), seed_ops=(), max_dist=8, max_c
                 "length": torch.cat([torch.ones((M, K1), dtype=torch.int32, device=dev), tm["length"]], 1).contiguous()}
     propose.wants_src = True
     return propose
+
+
+# ---- the offset at which the grid or the input best fits the answer's canvas ------------------------------------------------------
+ALIGN_GRID, ALIGN_INPUT = 1, 2  # ARCLE_ALIGN_*: slot s of the output <-> bit s
+
+
+def align_numpy(grid, grid_dim, inp, input_dim, answer, answer_dim, max_dist=None, sources=3, blank=True, full=False):
+    """The best offset of the grid and of the input of ONE state on the answer's canvas as arcle_align_rows reports it
+    (include/arcle_hip.h) — the host mirror, straight from the definition: every child grid is built and counted.  grid, inp, answer
+    int8 [H, W]; max_dist None: no limit; sources = ALIGN_GRID | ALIGN_INPUT; blank = what Paste does (True: the clip's whole
+    rectangle is written; False: its positive cells only).  -> (align int32 [2, 8] = ox, oy, correct, total, sh, sw, ah, aw per
+    source — slot 0 the grid, slot 1 the input; the slot of a source not asked for stays zero —, base (correct, total) of the grid
+    itself); full=True adds table int32 [2, 2H - 1, 2W - 1]: correct(ox, oy) at [ox + H - 1, oy + W - 1], -1 outside T, and children
+    int8 [2, 2H - 1, 2W - 1, H, W]: the child grid of every candidate on the whole plane.  The child of (ox, oy): the all-zero ah x aw
+    grid resize_grid leaves, with the clip — the source's rectangle [max(ox, 0), min(sh, ah + ox)) x [max(oy, 0), min(sw, aw + oy)) —
+    written with its corner at (max(-ox, 0), max(-oy, 0)); the candidates are -ah < ox < sh, -aw < oy < sw within max_dist; ties go to
+    the smaller |ox| + |oy|, then the smaller ox, then the smaller oy.  A dim of 0: (0, 0, 0, 0, sh, sw, ah, aw)."""
+    grid, inp, answer = (np.asarray(a).astype(np.int8) for a in (grid, inp, answer))
+    H, W = grid.shape
+    gh, gw = min(int(grid_dim[0]), H), min(int(grid_dim[1]), W)
+    ah, aw = min(int(answer_dim[0]), H), min(int(answer_dim[1]), W)
+    mh, mw = min(gh, ah), min(gw, aw)
+    D = 2 * (H + W) if max_dist is None else int(max_dist)
+    total = mh * mw + (abs(ah * aw - gh * gw) if (gh <= ah) == (gw <= aw) else abs(gh - ah) * mw + abs(gw - aw) * mh)
+    base = (int((grid[:mh, :mw] == answer[:mh, :mw]).sum()), total)
+    align = np.zeros((2, 8), np.int32)
+    table = np.full((2, 2 * H - 1, 2 * W - 1), -1, np.int32)
+    children = np.zeros((2, 2 * H - 1, 2 * W - 1, H, W), np.int8) if full else None
+    for s, (src, dim) in enumerate(((grid, grid_dim), (inp, input_dim))):
+        if not (int(sources) >> s) & 1:
+            continue
+        sh, sw = max(min(int(dim[0]), H), 0), max(min(int(dim[1]), W), 0)
+        best = None
+        some = min(sh, sw, ah, aw) >= 1  # (a dim of 0: T is empty)
+        for ox in range(1 - ah, sh) if some else ():
+            for oy in range(1 - aw, sw):
+                if abs(ox) + abs(oy) > D:
+                    continue
+                clip = src[max(ox, 0):min(sh, ah + ox), max(oy, 0):min(sw, aw + oy)]
+                child = np.zeros((H, W), np.int8)
+                px, py = max(-ox, 0), max(-oy, 0)
+                child[px:px + clip.shape[0], py:py + clip.shape[1]] = clip if blank else np.where(clip > 0, clip, 0)
+                c = int((child[:ah, :aw] == answer[:ah, :aw]).sum())
+                table[s, ox + H - 1, oy + W - 1] = c
+                if full:
+                    children[s, ox + H - 1, oy + W - 1] = child
+                key = (-c, abs(ox) + abs(oy), ox, oy)
+                if best is None or key < best:
+                    best = key
+        align[s] = (best[2], best[3], -best[0], ah * aw, sh, sw, ah, aw) if best is not None else (0, 0, 0, 0, sh, sw, ah, aw)
+    return (align, base, table, children) if full else (align, base)
+
+
+def _rect_bits(x1, x2, y1, y2, H, W):
+    """The bit rows (`pack_bits`) of the inclusive rectangles rows [x1, x2] x columns [y1, y2], tensors of one shape [...]: uint8 [..., 128]"""
+    dev = x1.device
+    r = torch.arange(H, device=dev).reshape(H, 1)
+    c = torch.arange(W, device=dev).reshape(1, W)
+    x1, x2, y1, y2 = (v.to(torch.int64).reshape(tuple(v.shape) + (1, 1)) for v in (x1, x2, y1, y2))
+    return pack_bits((r >= x1) & (r <= x2) & (c >= y1) & (c <= y2))
+
+
+def align_macros(alignments, copy_ops, resize_op, paste_op, H, W):
+    """The best offset of every source (`ARCVecEnv.align` -> Alignments) as ONE three-step macro per source: {"bits": uint8 [M, 2, 3, 128],
+    "operation": int32 [M, 2, 3], "length": int32 [M, 2]}.  Step 0 is the source's rectangle R = [max(ox, 0), min(sh, ah + ox)) x
+    [max(oy, 0), min(sw, aw + oy)) with the source's Copy — copy_ops = (Copy_O index, Copy_I index): slot 0 copies from the grid, slot
+    1 from the input —, step 1 the canvas rectangle (0, 0)..(ah - 1, aw - 1) with resize_op (resize_grid), step 2 the one-bit row of
+    P = (max(-ox, 0), max(-oy, 0)) with paste_op; H, W = the plane's size.  A slot with total == 0 (not asked for, or no candidate) or
+    that does not beat the row's own ratio — correct * base_total <= base_correct * total, in integers: this drops the identity, the
+    grid at (0, 0) under equal dims — gets operation -1 at step 0 and length 1: one ARCLE_ST_BAD_OP child, dropped by beam_search.
+    Built on the device from the eight words of each slot with `pack_bits`: no host synchronisation."""
+    a = alignments
+    dev = a.ox.device
+    M = int(a.ox.shape[0])
+    ox, oy = a.ox.to(torch.int64), a.oy.to(torch.int64)
+    sh, sw = a.src_dim[..., 0].to(torch.int64), a.src_dim[..., 1].to(torch.int64)
+    ah, aw = a.ans_dim[..., 0].to(torch.int64), a.ans_dim[..., 1].to(torch.int64)
+    zero = torch.zeros_like(ox)
+    bc, bt = a.base[:, 0].to(torch.int64).reshape(M, 1), a.base[:, 1].to(torch.int64).reshape(M, 1)
+    ok = (a.total > 0) & (a.correct.to(torch.int64) * bt > bc * a.total.to(torch.int64))
+    px, py = torch.maximum(-ox, zero), torch.maximum(-oy, zero)
+    bits = torch.stack([_rect_bits(torch.maximum(ox, zero), torch.minimum(sh, ah + ox) - 1, torch.maximum(oy, zero), torch.minimum(sw, aw + oy) - 1, H, W),
+                        _rect_bits(zero, ah - 1, zero, aw - 1, H, W), _rect_bits(px, px, py, py, H, W)], 2)
+    bits = torch.where(ok.reshape(M, 2, 1, 1), bits, torch.zeros((), dtype=torch.uint8, device=dev))
+    copy = torch.as_tensor([int(copy_ops[0]), int(copy_ops[1])], dtype=torch.int32, device=dev).reshape(1, 2)
+    op = torch.stack([copy.expand(M, 2), torch.full((M, 2), int(resize_op), dtype=torch.int32, device=dev),
+                      torch.full((M, 2), int(paste_op), dtype=torch.int32, device=dev)], 2)
+    op = torch.where(ok.reshape(M, 2, 1), op, torch.full((), -1, dtype=torch.int32, device=dev))
+    length = torch.where(ok, torch.full((), 3, dtype=torch.int32, device=dev), torch.ones((), dtype=torch.int32, device=dev))
+    return {"bits": bits.contiguous(), "operation": op.to(torch.int32).contiguous(), "length": length.to(torch.int32).contiguous()}
+
+
+def propose_alignments(copy_ops, resize_op, paste_op, blank=True, sources=3, max_dist=None, box_ops=(), seed_ops=(), max_components=16, skip_color=0,
+                       any_color=False, diagonal=False):
+    """A `propose` for beam_search that answers "at which offset does the grid, or the input, fit the answer's canvas?" — the one
+    proposer whose children have another grid_dim than their parent: at every depth, for each frontier state, ONE macro of three steps
+    per source asked for — the source's Copy on the rectangle the canvas covers, resize_op (resize_grid) to the answer's dims, paste_op
+    at the corner (`venv.align`, one launch; `align_macros`): K = 2, T = 3.  copy_ops = (Copy_O index, Copy_I index); blank must say
+    what paste_op does in the caller's table (True: paste_blank, both default tables).  With box_ops / seed_ops the singles of
+    `object_actions(masks=True)` on the objects of each state's grid come first, as macros of length 1, the way `propose_placements`
+    puts them: K = C * (len(box_ops) + len(seed_ops)) + 2.  It looks at the answer of each row's env, so it carries `wants_src = True`
+    and beam_search calls it with (venv, rows, src_env)."""
+    copy_ops, resize_op, paste_op = tuple(int(o) for o in copy_ops), int(resize_op), int(paste_op)
+    box_ops, seed_ops = list(box_ops), list(seed_ops)
+
+    def propose(venv, rows, src_env=None):
+        am = align_macros(venv.align(rows, src_env, max_dist, sources, blank), copy_ops, resize_op, paste_op, venv.H, venv.W)
+        if not box_ops and not seed_ops:
+            return am
+        if any_color or diagonal:
+            objs = venv.objects(rows, max_components=max_components, skip_color=skip_color, any_color=any_color, diagonal=diagonal, bits=True)
+        else:
+            objs = venv.components(rows, max_components=max_components, skip_color=skip_color, bits=True)
+        single = object_actions(objs, box_ops, seed_ops, masks=True)
+        M, K1 = (int(v) for v in single["operation"].shape)
+        dev = single["bits"].device
+        b1 = torch.zeros((M, K1, 3, int(single["bits"].shape[-1])), dtype=torch.uint8, device=dev)
+        b1[:, :, 0] = single["bits"]
+        o1 = torch.full((M, K1, 3), -1, dtype=torch.int32, device=dev)
+        o1[:, :, 0] = single["operation"]
+        return {"bits": torch.cat([b1, am["bits"]], 1).contiguous(), "operation": torch.cat([o1, am["operation"]], 1).contiguous(),
+                "length": torch.cat([torch.ones((M, K1), dtype=torch.int32, device=dev), am["length"]], 1).contiguous()}
+    propose.wants_src = True
+    return propose

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ARCLE_ABI_VERSION 14
+#define ARCLE_ABI_VERSION 15
 #define ARCLE_MAX_OPS 64
 #define ARCLE_MAX_CELLS 1024 /* H*W <= 1024: one 64-lane wavefront x 16 cells holds a plane (the one-wavefront-per-env kernels);
                                 larger planes (H, W <= 127) are served by the workgroup-per-env kernels — see "Grids beyond
@@ -626,6 +626,43 @@ int arcle_stamp_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t
 int arcle_turn_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, const int32_t* count,
                     const uint8_t* bits, const int32_t* src_env, int32_t max_dist, uint32_t turns, int32_t* turn, int32_t* base,
                     void* stream);
+/* The offset at which the GRID or the INPUT of a state row best fits the ANSWER'S CANVAS (ABI 15): for row m and each source asked for,
+ * the offset (ox, oy) at which the three-step macro
+ *   [Copy_src on R, resize_grid on the rectangle (0, 0)..(ah - 1, aw - 1), Paste on the single cell P]
+ * leaves the most correct cells, and that number, in closed form: no step is run.  The only sibling whose child has another grid_dim
+ * than its row: the macro leaves grid_dim = (ah, aw), so a task whose answer has another size than the grid can be solved.
+ *   rows, stride, src_env, base, stream   as for arcle_place_rows (rows NULL: the resident envs, n_rows <= n_envs).  There are no
+ *                 objects: no count, no bits.  Of a row only grid, grid_dim, input and input_dim are read
+ *   max_dist      offsets with |ox| + |oy| <= max_dist (any large max_dist means no limit)
+ *   sources       the set of sources asked for, ARCLE_ALIGN_* bits
+ *   blank         the paste_blank of the caller's Paste: 1 writes the clip's whole rectangle, 0 its positive cells only
+ *   align         int32 [n_rows][2][8] = ox, oy, correct, total, sh, sw, ah, aw; slot 0 is the grid, slot 1 the input.  Slots of sources
+ *                 not in `sources` are not written
+ * S is the source plane — the row's grid (ARCLE_ALIGN_GRID, copied by Copy_O, object.py:291-312) or the row's input (ARCLE_ALIGN_INPUT,
+ * copied by Copy_I, critical.py:39-46) — and (sh, sw) = min(its dim, (H, W)), clamped at 0; A is the answer of env src_env[m] and
+ * (ah, aw) = min(its answer_dim, (H, W)).  The candidates are
+ *   T = {(ox, oy) : -ah < ox < sh, -aw < oy < sw, |ox| + |oy| <= max_dist}
+ * — the copied rectangle R = [max(ox, 0), min(sh, ah + ox)) x [max(oy, 0), min(sw, aw + oy)) is never empty; (0, 0) is in T whenever
+ * all four dims are >= 1, and T is empty only when a dim is 0: the slot is then (0, 0, 0, 0, sh, sw, ah, aw).  resize_grid leaves an
+ * all-zero ah x aw grid, and Paste on P = (max(-ox, 0), max(-oy, 0)) writes the clip with its corner there, cut at the plane
+ * (object.py:340-348).  The child G'(ox, oy) is, for (i, j) in the canvas [0, ah) x [0, aw),
+ *   G'[i, j] = S[i + ox, j + oy]  if (i + ox, j + oy) lies inside (sh, sw) (blank = 0: and that byte, as int8, is > 0), else 0
+ * and 0 elsewhere on the plane: source bytes outside the source's dims are never read as anything but 0; with blank = 1 negative source
+ * bytes are carried over, with blank = 0 they become 0.  ox, oy >= 0 with full cover is "the answer is a window of the source";
+ * ox, oy <= 0 is "the source embedded in a larger canvas"; everything in between is a partial overlap.  correct(ox, oy) counts the
+ * cells of the canvas where G' equals A; total = ah * aw is the child's dense total (its dims equal the answer's), so the child is a
+ * goal exactly when correct == total.  The best offset maximises correct; ties go to the smaller |ox| + |oy|, then the smaller ox,
+ * then the smaller oy (arcle_place_rows' rule).  base is the dense pair of the row's own grid, as the siblings write it.  A row whose
+ * src_env names no env gets base = (0, 0) and all-zero slots.
+ * A one-step crop_grid form, turned or scaled sources and the objects of the input are out of scope.
+ * No side effects; allocates nothing: may be captured.  One wavefront per row.  Refusals, nothing written: n_rows <= 0, a stride below
+ * the row length, align NULL, max_dist < 0, sources == 0 or a bit above ARCLE_ALIGN_INPUT, blank outside {0, 1}, rows == NULL with
+ * n_rows > n_envs (with or without src_env: row m's grid is env m's): ARCLE_ERR_ARG; more than ARCLE_MAX_CELLS cells per plane, or an
+ * env kind without an answer plane: ARCLE_ERR_CONFIG. */
+#define ARCLE_ALIGN_GRID 1u  /* source = the row's grid (Copy_O) */
+#define ARCLE_ALIGN_INPUT 2u /* source = the row's input (Copy_I) */
+int arcle_align_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, const int32_t* src_env, int32_t max_dist,
+                     uint32_t sources, int32_t blank, int32_t* align, int32_t* base, void* stream);
 /* One state plane as a dense [n_envs][H*W] int8 array (device or pinned host memory), a strided copy on the stream: the
  * get_state()/set_state() of single keys of the reference's state dict. */
 int arcle_get_plane(arcle_env* env, int plane, int8_t* dst, void* stream);
