@@ -845,6 +845,44 @@ class EnvBatch:
                                             self._stream()), "arcle_align_rows")
         return out
 
+    def ray_rows(self, rows, count, bits, sets, free_color=0, through=False, src_env=None, best_bits=True, out=None):
+        """The lines each object of every state row casts toward the answer (arcle_ray_rows): rows, count, bits and src_env as for
+        `place_rows`; sets uint8 [S] on the device, 1 <= S <= 16 = one mask of directions per candidate (bit 0..7 = N, S, W, E, NW,
+        NE, SW, SE: _lib.RAY_*; a zero entry is the empty candidate); free_color = the byte (as int8) of the cells a ray may enter;
+        through = True: a ray runs over every cell outside the object to the edge of grid_dim.  Returns (ray int32 [M, C, S, 4] =
+        color, correct, cells, right; best int32 [M, C, 4] = set, color, correct, cells; best_bits uint8 [M, C, 128] or None; base
+        int32 [M, 2] = the dense pair of the row's own grid): per object and candidate the cells its rays cover — from the object's
+        own cells through free cells up to the first obstacle or the edge —, the colour c in 0..9 for which ONE `Color c` step on
+        them leaves the most correct cells (ties: the smaller c), that number and the cells of the answer the step gets right; per
+        object the candidate with the most correct (then the fewest cells, then the lowest index; set = -1: every candidate is
+        empty) and its cells as a bit row, the "bits" selection of `expand_rows` / `transition_rows`.  Entries k >= count are not
+        written; an empty candidate gives (0, base correct, 0, 0).  The definition: include/arcle_hip.h; its NumPy mirror:
+        arcle_amd.search.ray_numpy.  out: the four of a previous call with the same shapes (captured graphs; `sets` is read when
+        the launch runs).  Nothing of the batch is touched."""
+        assert bits.dtype == torch.uint8 and bits.dim() == 3 and bits.shape[2] == _lib.BITS_STRIDE and bits.is_contiguous()
+        assert sets.dtype == torch.uint8 and sets.dim() == 1 and sets.is_contiguous() and sets.device == bits.device
+        C, S = int(bits.shape[1]), int(sets.shape[0])
+        if rows is None:
+            M, ptr, stride = int(bits.shape[0]), None, 0
+        else:
+            assert rows.dtype == torch.int8 and rows.dim() == 2 and rows.stride(1) == 1
+            M, ptr, stride = int(rows.shape[0]), _ptr(rows), rows.stride(0)
+        assert int(bits.shape[0]) == M
+        assert count is None or (count.dtype == torch.int32 and tuple(count.shape) == (M, 2) and count.is_contiguous())
+        assert src_env is None or (src_env.dtype == torch.int32 and tuple(src_env.shape) == (M,) and src_env.is_contiguous())
+        if out is None:
+            out = (torch.zeros((M, C, S, 4), dtype=torch.int32, device=self.device), torch.zeros((M, C, 4), dtype=torch.int32, device=self.device),
+                   torch.zeros((M, C, _lib.BITS_STRIDE), dtype=torch.uint8, device=self.device) if best_bits else None,
+                   torch.zeros((M, 2), dtype=torch.int32, device=self.device))
+        ray, best, bbits, base = out
+        assert ray.dtype == torch.int32 and tuple(ray.shape) == (M, C, S, 4) and ray.is_contiguous()
+        assert best.dtype == torch.int32 and tuple(best.shape) == (M, C, 4) and best.is_contiguous()
+        assert bbits is None or (bbits.dtype == torch.uint8 and tuple(bbits.shape) == (M, C, _lib.BITS_STRIDE) and bbits.is_contiguous())
+        assert base is None or (base.dtype == torch.int32 and tuple(base.shape) == (M, 2) and base.is_contiguous())
+        self._check(self.L.arcle_ray_rows(self._h, M, ptr, stride, C, _ptr(count), _ptr(bits), _ptr(src_env), _ptr(sets), S, int(free_color),
+                                          int(bool(through)), _ptr(ray), _ptr(best), _ptr(bbits), _ptr(base), self._stream()), "arcle_ray_rows")
+        return out
+
     def get_plane(self, name, out=None):
         """One key of the state dict as a dense [N, H, W] int8 array (device tensor, or a pinned host tensor passed as `out`):
         arcle_get_plane, a strided copy on the current stream."""

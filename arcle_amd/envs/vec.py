@@ -40,6 +40,10 @@ Turns = collections.namedtuple("Turns", "dx dy correct valid base")
 # the source on the answer's canvas, its correct cells, the child's total, the source's and the answer's dims) and the dense pair of
 # every row's own grid
 Alignments = collections.namedtuple("Alignments", "ox oy correct total src_dim ans_dim base")
+# what ARCVecEnv.rays returns: views of one int32 [M, C, S, 4] buffer (per object and set of directions the colour one Color step on the
+# rays' cells should paint, the correct cells it leaves, the rays' cells, the cells it gets right), of one int32 [M, C, 4] buffer (the
+# best set of every object, its colour, correct cells and cells), that set's cells as bit rows and the dense pair of every row's own grid
+Rays = collections.namedtuple("Rays", "color correct cells right best_set best_color best_correct best_cells best_bits base")
 
 
 def _table_of(env_cls, **ctor_kw):
@@ -745,6 +749,30 @@ class ARCVecEnv:
             src_env = src_env.to(device=self.device, dtype=torch.int32).contiguous()
         al, base = self.batch.align_rows(rows, src_env, max_dist, sources, blank)
         return Alignments(al[..., 0], al[..., 1], al[..., 2], al[..., 3], al[..., 4:6], al[..., 6:8], base)
+
+    def rays(self, rows, objs, sets=None, free_color=0, through=False, src_env=None, bits=True):
+        """The lines each object casts toward the answer (arcle_ray_rows, one launch; no step is run): objs, rows and src_env as for
+        `place`; sets = the candidates, one mask of directions each (bit 0..7 = N, S, W, E, NW, NE, SW, SE; at most 16; None: the 13
+        of `search.RAY_SETS` — the eight single directions, N|S, W|E, the orthogonal four, the diagonal four, all eight);
+        free_color = the byte of the cells a ray may enter (0: the background); through = True: a ray runs over everything to the
+        edge of grid_dim.  Returns a Rays of device tensors: color, correct, cells, right [M, C, S] = per object and candidate the
+        colour c for which ONE `Color c` step on the rays' cells leaves the most correct cells, that number, the cells the rays
+        cover and the cells the step gets right; best_set, best_color, best_correct, best_cells [M, C] = the candidate with the
+        most correct (then the fewest cells, then the lowest index; best_set -1: every candidate is empty); best_bits [M, C, 128] =
+        its cells as a bit row, a "bits" selection for `expand` / `transition` (None with bits=False); base [M, 2] = the dense pair
+        of the row's own grid.  Entries k >= count are zero.  `search.ray_actions` turns it into one Color step per object.  This
+        env's state is not touched."""
+        assert objs.bits is not None, "rays needs the objects' bit rows (bits=True)"
+        count = torch.stack([objs.count, objs.left], 1).to(torch.int32).contiguous()
+        if src_env is not None:
+            src_env = src_env.to(device=self.device, dtype=torch.int32).contiguous()
+        if sets is None:
+            from .. import search
+            sets = search.RAY_SETS
+        sets = torch.as_tensor([int(s) for s in sets], dtype=torch.uint8, device=self.device) if not torch.is_tensor(sets) else \
+            sets.to(device=self.device, dtype=torch.uint8).contiguous()
+        ray, best, bbits, base = self.batch.ray_rows(rows, count, objs.bits.contiguous(), sets, free_color, through, src_env, bits)
+        return Rays(ray[..., 0], ray[..., 1], ray[..., 2], ray[..., 3], best[..., 0], best[..., 1], best[..., 2], best[..., 3], bbits, base)
 
     def autotune(self, payload, operation=None, form="bbox"):
         """Times every launch plan the library has for this env's steps (self-ordering or not, the cache policies of the speculative grid

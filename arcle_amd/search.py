@@ -4,7 +4,9 @@ search, and the objects of a grid as candidate actions (`components_numpy`: the 
 bounding boxes, or with masks=True their exact cells as bit rows; `pack_bits` / `unpack_bits`: that layout in torch), and where each
 object best fits the answer (`place_numpy`: the host mirror of arcle_place_rows; `placement_macros` / `propose_placements`: the
 best translation of every object as ONE Move macro), and where a COPY of each object best fits it (`stamp_numpy`: the host mirror of
-arcle_stamp_rows; `stamp_macros` / `propose_stamps`: the best paste position of every object as ONE CopyO + Paste macro).
+arcle_stamp_rows; `stamp_macros` / `propose_stamps`: the best paste position of every object as ONE CopyO + Paste macro), and the
+lines each object casts toward the answer (`ray_numpy`: the host mirror of arcle_ray_rows; `ray_actions` / `propose_rays`: the best
+set of rays of every object as ONE Color step).
 
 The hash is defined in include/arcle_hip.h (next to arcle_hash_rows) and computed on the device by arcle_amd/csrc/arcle_search.h;
 `hash_rows_numpy` restates it on the host — the same arrangement as arcle_amd/sampling.py for the device RNG — and is what the tests
@@ -920,5 +922,114 @@ def propose_alignments(copy_ops, resize_op, paste_op, blank=True, sources=3, max
         o1[:, :, 0] = single["operation"]
         return {"bits": torch.cat([b1, am["bits"]], 1).contiguous(), "operation": torch.cat([o1, am["operation"]], 1).contiguous(),
                 "length": torch.cat([torch.ones((M, K1), dtype=torch.int32, device=dev), am["length"]], 1).contiguous()}
+    propose.wants_src = True
+    return propose
+
+
+# ---- the lines each object casts toward the answer ---------------------------------------------------------------------------------
+# bit d of a direction mask (ARCLE_RAY_*) -> (dx, dy): N, S, W, E, NW, NE, SW, SE; x runs along rows
+RAY_DIRS = ((-1, 0), (1, 0), (0, -1), (0, 1), (-1, -1), (-1, 1), (1, -1), (1, 1))
+# the default candidates of `ARCVecEnv.rays` / `propose_rays`: the eight single directions, N|S, W|E, the orthogonal four, the diagonal
+# four, all eight
+RAY_SETS = (1, 2, 4, 8, 16, 32, 64, 128, 3, 12, 15, 240, 255)
+
+
+def ray_numpy(grid, grid_dim, answer, answer_dim, masks, sets=None, free_color=0, through=False, full=False):
+    """The rays of every object of ONE grid as arcle_ray_rows reports them (include/arcle_hip.h) — the host mirror, straight from the
+    definition and deliberately not a bit-board algorithm: from every cell of the object a walk in every direction, cell by cell.
+    grid, answer int8 [H, W]; masks [n, H, W] (truthy = the object's cells; cells outside grid_dim are ignored); sets: direction masks
+    (bit 0..7 = N, S, W, E, NW, NE, SW, SE; None: RAY_SETS); free_color: the byte (as int8) a ray may enter; through=True: a ray
+    enters every cell of grid_dim outside the object.  -> (ray int32 [n, S, 4] = color, correct, cells, right; best int32 [n, 4] =
+    set, color, correct, cells; base (correct, total) of the grid itself); full=True adds cells bool [n, S, H, W]: every candidate's
+    selection.  A walk starts at a cell of B, takes the next cell while it lies inside grid_dim, is not in B and (through, or its byte
+    is free_color), and stops at the first that is not.  color = the c in 0..9 most frequent in the answer under the candidate's cells
+    inside the common rectangle (ties: the smaller c), right = that frequency, correct = the correct cells of the grid with those
+    cells painted c.  An empty candidate: (0, base correct, 0, 0).  best: the most correct among the non-empty candidates, then the
+    fewest cells, then the lowest set; none: (-1, 0, base correct, 0)."""
+    grid, answer = np.asarray(grid).astype(np.int8), np.asarray(answer).astype(np.int8)
+    H, W = grid.shape
+    gh, gw = min(int(grid_dim[0]), H), min(int(grid_dim[1]), W)
+    ah, aw = min(int(answer_dim[0]), H), min(int(answer_dim[1]), W)
+    mh, mw = min(gh, ah), min(gw, aw)
+    total = mh * mw + (abs(ah * aw - gh * gw) if (gh <= ah) == (gw <= aw) else abs(gh - ah) * mw + abs(gw - aw) * mh)
+    base = (int((grid[:mh, :mw] == answer[:mh, :mw]).sum()), total)
+    sets = [int(s) & 255 for s in (RAY_SETS if sets is None else sets)]
+    fc = (int(free_color) + 128) % 256 - 128
+    masks = np.asarray(masks).reshape(-1, H, W)
+    n, S_ = masks.shape[0], len(sets)
+    ray, best = np.zeros((n, S_, 4), np.int32), np.zeros((n, 4), np.int32)
+    cells = np.zeros((n, S_, H, W), bool)
+    for k in range(n):
+        B = np.zeros((H, W), bool)
+        B[:gh, :gw] = masks[k, :gh, :gw] != 0
+        per_dir = np.zeros((8, H, W), bool)
+        for x, y in np.argwhere(B):
+            for d, (dx, dy) in enumerate(RAY_DIRS):
+                i, j = x + dx, y + dy
+                while 0 <= i < gh and 0 <= j < gw and not B[i, j] and (through or grid[i, j] == fc):
+                    per_dir[d, i, j] = True
+                    i, j = i + dx, j + dy
+        top = None
+        for s, m in enumerate(sets):
+            R = np.zeros((H, W), bool)
+            for d in range(8):
+                if (m >> d) & 1:
+                    R |= per_dir[d]
+            cells[k, s] = R
+            if not R.any():
+                ray[k, s] = (0, base[0], 0, 0)
+                continue
+            under = answer[:mh, :mw][R[:mh, :mw]]
+            freq = [int((under == c).sum()) for c in range(10)]
+            color = int(np.argmax(freq))  # (the first maximum: the smaller c)
+            child = grid.copy()
+            child[R] = color
+            ray[k, s] = (color, int((child[:mh, :mw] == answer[:mh, :mw]).sum()), int(R.sum()), freq[color])
+            key = (-int(ray[k, s, 1]), int(ray[k, s, 2]), s)
+            if top is None or key < top:
+                top = key
+        best[k] = (-1, 0, base[0], 0) if top is None else (top[2], ray[k, top[2], 0], -top[0], top[1])
+    return (ray, best, base, cells) if full else (ray, best, base)
+
+
+def ray_actions(objs, rays, color_ops):
+    """The best ray candidate of every object (`ARCVecEnv.rays` -> Rays, with its bit rows) as ONE single-step candidate per object:
+    {"bits": uint8 [M, C, 128] = rays.best_bits, "operation": int32 [M, C] = color_ops[best_color]} — color_ops[c] = the index of
+    `Color c` in the caller's op table, c = 0..9.  Slots with k >= count, without a candidate (best_set < 0) or whose step would not
+    gain (best_correct <= base correct) get operation -1 and a zero bit row: an ARCLE_ST_BAD_OP child, dropped by beam_search.  Pure
+    indexing on the device: no host synchronisation."""
+    assert rays.best_bits is not None, "ray_actions needs the candidates' bit rows (rays(bits=True))"
+    dev = rays.best_bits.device
+    M, C = (int(v) for v in rays.best_set.shape)
+    ops = torch.as_tensor(list(color_ops), dtype=torch.int32, device=dev)
+    assert int(ops.numel()) == 10, "color_ops: the ten Color ops, color_ops[c] paints c"
+    there = torch.arange(C, device=dev).reshape(1, C) < objs.count.reshape(M, 1)
+    ok = there & (rays.best_set >= 0) & (rays.best_correct > rays.base[:, 0].reshape(M, 1))
+    op = torch.where(ok, ops[rays.best_color.clamp(0, 9).to(torch.int64)], torch.full((), -1, dtype=torch.int32, device=dev))
+    bits = torch.where(ok.reshape(M, C, 1), rays.best_bits, torch.zeros((), dtype=torch.uint8, device=dev))
+    return {"bits": bits.contiguous(), "operation": op.to(torch.int32).contiguous()}
+
+
+def propose_rays(color_ops, sets=None, free_color=0, through=False, box_ops=(), seed_ops=(), max_components=16, skip_color=0, any_color=False,
+                 diagonal=False):
+    """A `propose` for beam_search that answers "which lines does this object cast?": at every depth the objects of each frontier
+    state's grid (`venv.objects` / `venv.components` with their bit rows), first the singles of `object_actions(masks=True)` — box_ops
+    on the objects' exact cells, seed_ops on their seeds — then for every object ONE step: `Color c` on the cells of its best set of
+    rays (`venv.rays`, one launch; `ray_actions`), K = C * (len(box_ops) + len(seed_ops) + 1).  color_ops[c] = the index of `Color c`
+    in the env's op table (both default tables: range(10)); sets, free_color, through as for `ARCVecEnv.rays`.  These are single
+    steps: beam_search takes them through `venv.expand` / `venv.transition`.  It looks at the answer of each row's env, so it carries
+    `wants_src = True` and beam_search calls it with (venv, rows, src_env)."""
+    color_ops, box_ops, seed_ops = [int(o) for o in color_ops], list(box_ops), list(seed_ops)
+
+    def propose(venv, rows, src_env=None):
+        if any_color or diagonal:
+            objs = venv.objects(rows, max_components=max_components, skip_color=skip_color, any_color=any_color, diagonal=diagonal, bits=True)
+        else:
+            objs = venv.components(rows, max_components=max_components, skip_color=skip_color, bits=True)
+        ra = ray_actions(objs, venv.rays(rows, objs, sets, free_color, through, src_env), color_ops)
+        if not box_ops and not seed_ops:
+            return ra
+        single = object_actions(objs, box_ops, seed_ops, masks=True)
+        return {"bits": torch.cat([single["bits"], ra["bits"]], 1).contiguous(), "operation": torch.cat([single["operation"], ra["operation"]], 1).contiguous()}
     propose.wants_src = True
     return propose

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ARCLE_ABI_VERSION 15
+#define ARCLE_ABI_VERSION 16
 #define ARCLE_MAX_OPS 64
 #define ARCLE_MAX_CELLS 1024 /* H*W <= 1024: one 64-lane wavefront x 16 cells holds a plane (the one-wavefront-per-env kernels);
                                 larger planes (H, W <= 127) are served by the workgroup-per-env kernels — see "Grids beyond
@@ -663,6 +663,62 @@ int arcle_turn_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t 
 #define ARCLE_ALIGN_INPUT 2u /* source = the row's input (Copy_I) */
 int arcle_align_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, const int32_t* src_env, int32_t max_dist,
                      uint32_t sources, int32_t blank, int32_t* align, int32_t* base, void* stream);
+/* The LINES each object of a state row casts toward the answer (ABI 16): for object k of row m — a bit row as for arcle_place_rows — and
+ * each of n_sets sets of directions, the cells its rays cover, the colour c for which ONE `Color c` step on exactly those cells
+ * (color.py:70-77) leaves the most correct cells, and that number, in closed form: no step is run.  The only sibling that draws: the
+ * child holds cells that no object of the row holds ("extend every pixel to the border", "shoot a line until it hits a wall", "a cross
+ * or a star through each seed").
+ *   rows, stride, max_comp, count, bits, src_env, base, stream   as for arcle_place_rows
+ *   sets          uint8 [n_sets], 1 <= n_sets <= 16, the same for all rows: DEVICE memory, read by the kernel when the launch runs (like
+ *                 the op table: a captured launch sees the bytes it holds at replay).  Entry s is a mask of ARCLE_RAY_* directions; a
+ *                 zero entry is allowed and is the empty candidate
+ *   free_color    through = 0: the int8 byte of the cells a ray may enter, -128 .. 127 (callers pass 0: the background)
+ *   through       0: a ray stops in front of the first cell whose byte is not free_color; 1: it runs over every cell to the edge
+ *   ray           int32 [n_rows][max_comp][n_sets][4] = color, correct, cells, right; slots of objects k >= count are not written
+ *   best          int32 [n_rows][max_comp][4] = set, color, correct, cells; likewise
+ *   best_bits     optional uint8 [n_rows][max_comp][arcle_mask_bits_stride()], 2-byte aligned: the best candidate's cells in the bit-row
+ *                 format of arcle_expand_rows / arcle_transition_rows (ARCLE_INGRESS_BITS) — the selection of the step, made on the
+ *                 device; all arcle_mask_bits_stride() bytes of a written slot are written
+ * BOARDS.  G is the row's grid, (gh, gw) = min(grid_dim, (H, W)); A and (ah, aw) = min(answer_dim, (H, W)) are the answer of env
+ * src_env[m]; (mh, mw) = min((gh, gw), (ah, aw)) is the common rectangle; B is the cells of the bit row inside [0, gh) x [0, gw) (bits
+ * outside it or at indices >= H * W are ignored).  x runs along rows (down), y along columns, as everywhere in this ABI.
+ * DIRECTIONS.  Bit 0..7 of a mask: N (-1, 0), S (+1, 0), W (0, -1), E (0, +1), NW (-1, -1), NE (-1, +1), SW (+1, -1), SE (+1, +1) as
+ * (dx, dy).  shift_d(X) = {(x + dx, y + dy) : (x, y) in X}.
+ * FREE CELLS.  F = the cells of [0, gh) x [0, gw) that are not in B and, with through = 0, whose grid byte equals free_color as int8;
+ * with through = 1, all of them.
+ * RAY.  R_d is the least board with R_d = shift_d(B | R_d) & F: walk from every cell of B in direction d and take cells while they are
+ * in F.  A ray starts only next to B's own cells (it does not jump a gap), stops in front of the first cell that is not free or at the
+ * edge of grid_dim, and never wraps from one row or column into the next.  Cells of B never belong to a ray; a ray may cross a hole
+ * that B encloses only where the hole's cells are free, and goes on behind a further cell of B only as that cell's own ray.
+ * CANDIDATES.  Candidate s of an object is R_s = the union of R_d over the directions d in sets[s]; its step is ONE `Color c` on the
+ * selection R_s, whose child is G with R_s's cells set to c: grid_dim and the dense total do not change.  With K = the cells of the
+ * common rectangle at which G equals A,
+ *   cells   = |R_s|
+ *   right   = max over c in 0..9 of |{(x, y) in R_s, inside the common rectangle, A[x, y] == c}|,  color = the smallest c reaching it
+ *   correct = base correct - |R_s & K| + right      — the first number of the child's dense pair
+ * and an empty R_s (a zero set, an empty B, no free neighbour) gives the slot (0, base correct, 0, 0).
+ * BEST.  Among the candidates with cells > 0 the one with the most correct; ties go to fewer cells, then to the lower set index:
+ * (set, color, correct, cells) and R_set in best_bits.  If every candidate is empty: (-1, 0, base correct, 0) and an all-zero bit row.
+ * base is the dense pair of the row's own grid, as the siblings write it.  A row whose src_env names no env gets base = (0, 0) and
+ * zeros in all slots of its objects (ray, best and best_bits).
+ * Out of scope: handles of more than ARCLE_MAX_CELLS cells; a limit on a ray's length; rays of more than one colour or of a colour
+ * no single Color step gives (a ray that takes its object's colour is `Color` of that colour: it is scored, but only the best c is
+ * reported); rays started from the cells of the INPUT instead of the grid's objects.
+ * No side effects; allocates nothing: may be captured.  One wavefront per row.  Refusals, nothing written: those of arcle_place_rows
+ * (without max_dist), sets, ray or best NULL, n_sets outside [1, 16], an odd best_bits address, through outside {0, 1}, free_color
+ * outside [-128, 127]: ARCLE_ERR_ARG; more than ARCLE_MAX_CELLS cells per plane, or an env kind without an answer plane:
+ * ARCLE_ERR_CONFIG. */
+#define ARCLE_RAY_N 1u
+#define ARCLE_RAY_S 2u
+#define ARCLE_RAY_W 4u
+#define ARCLE_RAY_E 8u
+#define ARCLE_RAY_NW 16u
+#define ARCLE_RAY_NE 32u
+#define ARCLE_RAY_SW 64u
+#define ARCLE_RAY_SE 128u
+int arcle_ray_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, const int32_t* count,
+                   const uint8_t* bits, const int32_t* src_env, const uint8_t* sets, int32_t n_sets, int32_t free_color,
+                   int32_t through, int32_t* ray, int32_t* best, uint8_t* best_bits, int32_t* base, void* stream);
 /* One state plane as a dense [n_envs][H*W] int8 array (device or pinned host memory), a strided copy on the stream: the
  * get_state()/set_state() of single keys of the reference's state dict. */
 int arcle_get_plane(arcle_env* env, int plane, int8_t* dst, void* stream);
