@@ -221,6 +221,7 @@ ARCLE_DEV void touch_args(const void* a, const void* b) { asm volatile("" ::"s"(
 #include "arcle_turn.h"        // the translation at which each object best fits the answer after a rotation or a flip (arcle_turn_rows)
 #include "arcle_align.h"       // the offset at which the grid or the input best fits the answer's canvas (arcle_align_rows)
 #include "arcle_ray.h"         // the lines each object casts toward the answer (arcle_ray_rows)
+#include "arcle_mirror.h"      // each object's box filled from its mirror image (arcle_mirror_rows)
 #include "arcle_big_params.h"  // grids beyond ARCLE_MAX_CELLS: one workgroup per env (arcle_big.hip)
 
 using arcle::StepParams;
@@ -559,6 +560,14 @@ __global__ __launch_bounds__(64 * COMP_WAVES_PER_WG) void arcle_ray_kernel(const
   const int row = wave_of_launch(COMP_WAVES_PER_WG);
   if (row >= x.p.n_envs) return;
   arcle::wave_ray_row<FW, FLAT>(x, nullptr, nullptr, row, (int)(threadIdx.x & 63));
+}
+
+// arcle_mirror_rows: likewise
+template <int FW>
+__global__ __launch_bounds__(64 * COMP_WAVES_PER_WG) void arcle_mirror_kernel(const arcle::MirrorParams x) {
+  const int row = wave_of_launch(COMP_WAVES_PER_WG);
+  if (row >= x.p.n_envs) return;
+  arcle::wave_mirror_row<FW>(x, nullptr, nullptr, row, (int)(threadIdx.x & 63));
 }
 
 __global__ __launch_bounds__(64 * WAVES_PER_WG) void arcle_reset_kernel(const StepParams p) {
@@ -2477,6 +2486,49 @@ extern "C" int arcle_ray_rows(arcle_env* e, int32_t n_rows, const int8_t* rows, 
   if (width_class(e->base) != arcle::FW_GENERIC) hipLaunchKernelGGL((arcle_ray_kernel<arcle::FW_FAST, false>), g, b, 0, (hipStream_t)stream, x);
   else if (e->base.W <= 32 && e->base.H <= 64) hipLaunchKernelGGL((arcle_ray_kernel<arcle::FW_GENERIC, false>), g, b, 0, (hipStream_t)stream, x);
   else hipLaunchKernelGGL((arcle_ray_kernel<arcle::FW_GENERIC, true>), g, b, 0, (hipStream_t)stream, x);
+  HIP_TRY(e, hipGetLastError());
+  return ARCLE_OK;
+}
+
+// the best source rectangle of every object of every row under each symmetry asked for (arcle_mirror.h): reads what arcle_place_rows
+// reads, writes the caller's arrays — nothing of the handle is written
+extern "C" int arcle_mirror_rows(arcle_env* e, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, const int32_t* count,
+                                 const uint8_t* bits, const int32_t* src_env, int32_t max_dist, uint32_t mirrors, int32_t blank,
+                                 int32_t* mirror, int32_t* base, void* stream) {
+  if (!e || !bits || !mirror) return ARCLE_ERR_ARG;
+  if (n_rows <= 0) return fail(e, ARCLE_ERR_ARG, "n_rows must be positive");
+  if (e->big) return fail(e, ARCLE_ERR_CONFIG, "arcle_mirror_rows: handles of at most 1024 cells per plane (ARCLE_MAX_CELLS)");
+  if (!e->bufs.plane[ARCLE_PL_ANSWER]) return fail(e, ARCLE_ERR_CONFIG, "arcle_mirror_rows needs the answer plane");
+  if (max_comp < 1 || max_comp > ARCLE_MAX_CELLS) return fail(e, ARCLE_ERR_ARG, "arcle_mirror_rows: max_comp in [1, ARCLE_MAX_CELLS]");
+  if (max_dist < 0) return fail(e, ARCLE_ERR_ARG, "arcle_mirror_rows: max_dist must not be negative");
+  if (mirrors == 0u || mirrors > (ARCLE_MIRROR_H | ARCLE_MIRROR_V | ARCLE_MIRROR_POINT))
+    return fail(e, ARCLE_ERR_ARG, "arcle_mirror_rows: mirrors is a non-empty set of ARCLE_MIRROR_* bits");
+  if (blank != 0 && blank != 1) return fail(e, ARCLE_ERR_ARG, "arcle_mirror_rows: blank is 0 or 1");
+  if ((uintptr_t)bits & 1u) return fail(e, ARCLE_ERR_ARG, "arcle_mirror_rows: bit rows must be 2-byte aligned");
+  if (rows) {
+    if (int rc = check_rows(e, rows, stride, 0)) return rc;
+  } else if (n_rows > e->cfg.n_envs) {
+    return fail(e, ARCLE_ERR_ARG, "arcle_mirror_rows: rows == NULL takes the resident envs (n_rows <= n_envs)");
+  }
+  DeviceGuard guard(e->device);
+  arcle::MirrorParams x = {};
+  x.p = e->base;
+  x.p.n_resident = x.p.n_envs;
+  x.p.n_envs = n_rows;
+  x.p.rows_in = rows;
+  x.p.rows_in_stride = rows ? stride : 0;
+  x.max_comp = max_comp;
+  x.max_dist = max_dist > 2 * ARCLE_MAX_CELLS ? 2 * ARCLE_MAX_CELLS : max_dist;  // (no candidate is farther: the sums stay small)
+  x.count = count;
+  x.bits = bits;
+  x.src_env = src_env;
+  x.mirror = mirror;
+  x.base = base;
+  x.mirrors = mirrors;
+  x.blank = blank;
+  const dim3 g = grid_for(n_rows, COMP_WAVES_PER_WG), b(64 * COMP_WAVES_PER_WG);
+  if (width_class(e->base) != arcle::FW_GENERIC) hipLaunchKernelGGL(arcle_mirror_kernel<arcle::FW_FAST>, g, b, 0, (hipStream_t)stream, x);
+  else hipLaunchKernelGGL(arcle_mirror_kernel<arcle::FW_GENERIC>, g, b, 0, (hipStream_t)stream, x);
   HIP_TRY(e, hipGetLastError());
   return ARCLE_OK;
 }

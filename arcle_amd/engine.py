@@ -817,6 +817,36 @@ class EnvBatch:
                                            _ptr(turn), _ptr(base), self._stream()), "arcle_turn_rows")
         return out
 
+    def mirror_rows(self, rows, count, bits, src_env=None, max_dist=None, mirrors=7, blank=True, out=None):
+        """Each object's box filled from its mirror image (arcle_mirror_rows): rows, count, bits, src_env and max_dist as for
+        `place_rows`; mirrors = the set of symmetries asked for (bit s = slot s: left-right H, up-down V, the point reflection;
+        _lib.MIRROR_*); blank = what the table's Paste does (True: paste_blank, both default tables).  Returns (mirror int32 [M, C, 3,
+        4] = dx, dy, correct, valid per symmetry, base int32 [M, 2] = the dense pair of the row's own grid): per symmetry the source
+        rectangle — the object's box moved dx rows down and dy columns right, inside grid_dim; dx = 0 under H, dy = 0 under V — whose
+        flipped copy, written over the box (CopyO + Paste + Flip), scores the most correct cells, ties to the nearer one, then the
+        smaller dx, then the smaller dy.  Slots of symmetries not asked for and entries k >= count are not written (zero in a fresh
+        output).  The definition: include/arcle_hip.h; its NumPy mirror: arcle_amd.search.mirror_numpy.  out: the pair of a previous
+        call with the same shapes (captured graphs).  Nothing of the batch is touched."""
+        assert bits.dtype == torch.uint8 and bits.dim() == 3 and bits.shape[2] == _lib.BITS_STRIDE and bits.is_contiguous()
+        C = int(bits.shape[1])
+        if rows is None:
+            M, ptr, stride = int(bits.shape[0]), None, 0
+        else:
+            assert rows.dtype == torch.int8 and rows.dim() == 2 and rows.stride(1) == 1
+            M, ptr, stride = int(rows.shape[0]), _ptr(rows), rows.stride(0)
+        assert int(bits.shape[0]) == M
+        assert count is None or (count.dtype == torch.int32 and tuple(count.shape) == (M, 2) and count.is_contiguous())
+        assert src_env is None or (src_env.dtype == torch.int32 and tuple(src_env.shape) == (M,) and src_env.is_contiguous())
+        if out is None:
+            out = (torch.zeros((M, C, 3, 4), dtype=torch.int32, device=self.device), torch.zeros((M, 2), dtype=torch.int32, device=self.device))
+        mirror, base = out
+        assert mirror.dtype == torch.int32 and tuple(mirror.shape) == (M, C, 3, 4) and mirror.is_contiguous()
+        assert base is None or (base.dtype == torch.int32 and tuple(base.shape) == (M, 2) and base.is_contiguous())
+        D = 0x7fffffff if max_dist is None else int(max_dist)
+        self._check(self.L.arcle_mirror_rows(self._h, M, ptr, stride, C, _ptr(count), _ptr(bits), _ptr(src_env), D, int(mirrors),
+                                             int(bool(blank)), _ptr(mirror), _ptr(base), self._stream()), "arcle_mirror_rows")
+        return out
+
     def align_rows(self, rows=None, src_env=None, max_dist=None, sources=3, blank=True, out=None):
         """The offset at which the grid or the input of every state row best fits the answer's canvas (arcle_align_rows): rows int8
         [M, >= L] state rows (None: the resident envs, M = N, or the length of src_env / of `out`), src_env and max_dist as for

@@ -36,6 +36,10 @@ Stamps = collections.namedtuple("Stamps", "px py correct cells base")
 # what ARCVecEnv.turn returns: views of one int32 [M, C, 5, 4] buffer (per turn — Rotate 90, 180, 270, Flip H, Flip V — the best
 # translation of every object after it, its correct cells, whether the turn has a candidate) and the dense pair of every row's own grid
 Turns = collections.namedtuple("Turns", "dx dy correct valid base")
+# what ARCVecEnv.mirror returns: views of one int32 [M, C, 3, 4] buffer (per object and symmetry — left-right, up-down, point — the
+# source rectangle whose flipped copy best fills the object's box, its correct cells, whether there is one) and the dense pair of every
+# row's own grid
+Mirrors = collections.namedtuple("Mirrors", "dx dy correct valid base")
 # what ARCVecEnv.align returns: views of one int32 [M, 2, 8] buffer (per source — the row's grid, the row's input — the best offset of
 # the source on the answer's canvas, its correct cells, the child's total, the source's and the answer's dims) and the dense pair of
 # every row's own grid
@@ -734,6 +738,22 @@ class ARCVecEnv:
             src_env = src_env.to(device=self.device, dtype=torch.int32).contiguous()
         turn, base = self.batch.turn_rows(rows, count, objs.bits.contiguous(), src_env, max_dist, turns)
         return Turns(turn[..., 0], turn[..., 1], turn[..., 2], turn[..., 3], base)
+
+    def mirror(self, rows, objs, src_env=None, max_dist=None, mirrors=7, blank=True):
+        """Each object's box filled from its mirror image (arcle_mirror_rows, one launch; no step is run): objs, rows and src_env as
+        for `place`; max_dist = |dx| + |dy| of the source rectangle at most (None: no limit); mirrors = the set of symmetries asked
+        for, bit s = slot s: left-right (H), up-down (V), the point reflection; blank = what the table's Paste does (True:
+        paste_blank, both default tables).  Returns a Mirrors of device tensors: dx, dy [M, C, 3] = per symmetry the source rectangle
+        (the object's box moved by (dx, dy), inside grid_dim) whose flipped copy over the box — CopyO + Paste + Flip — leaves the most
+        correct cells, ties to the nearer one; correct [M, C, 3] = that number; valid [M, C, 3] = 1 (0: no candidate); base [M, 2] =
+        the dense pair of the row's own grid.  Slots of symmetries not asked for and entries k >= count are zero.
+        `search.mirror_macros` turns it into one macro per object.  This env's state is not touched."""
+        assert objs.bits is not None, "mirror needs the objects' bit rows (bits=True)"
+        count = torch.stack([objs.count, objs.left], 1).to(torch.int32).contiguous()
+        if src_env is not None:
+            src_env = src_env.to(device=self.device, dtype=torch.int32).contiguous()
+        mirror, base = self.batch.mirror_rows(rows, count, objs.bits.contiguous(), src_env, max_dist, mirrors, blank)
+        return Mirrors(mirror[..., 0], mirror[..., 1], mirror[..., 2], mirror[..., 3], base)
 
     def align(self, rows, src_env=None, max_dist=None, sources=3, blank=True):
         """The offset at which the grid or the input of every state row best fits the answer's canvas (arcle_align_rows, one launch;

@@ -1033,3 +1033,146 @@ def propose_rays(color_ops, sets=None, free_color=0, through=False, box_ops=(), 
         return {"bits": torch.cat([single["bits"], ra["bits"]], 1).contiguous(), "operation": torch.cat([single["operation"], ra["operation"]], 1).contiguous()}
     propose.wants_src = True
     return propose
+
+
+# ---- each object's box filled from its mirror image ---------------------------------------------------------------------------------
+MIRROR_H, MIRROR_V, MIRROR_POINT = 1, 2, 4  # ARCLE_MIRROR_*: slot s of the output <-> bit s
+
+
+def _flipped(tile, s):
+    return (np.fliplr(tile), np.flipud(tile), np.flipud(np.fliplr(tile)))[s]
+
+
+def mirror_numpy(grid, grid_dim, answer, answer_dim, masks, max_dist=None, mirrors=7, blank=True, full=False):
+    """The best source rectangle of every object of ONE grid under each of the three symmetries, as arcle_mirror_rows reports it
+    (include/arcle_hip.h) — the host mirror, straight from the definition: every child grid is built with np.fliplr / np.flipud and
+    counted.  grid, answer int8 [H, W]; masks [n, H, W] (truthy = the object's cells; cells outside grid_dim are ignored); max_dist
+    None: no limit; mirrors = the mask of the symmetries asked for (bit s = slot s: left-right H, up-down V, point); blank = what
+    Paste does (True: the clip's whole rectangle is written; False: its positive cells only).  -> (mirror int32 [n, 3, 4] = dx, dy,
+    correct, valid — zeros in the slots not asked for —, base (correct, total) of the grid itself); full=True adds table int32 [n, 3,
+    2H - 1, 2W - 1]: correct(s, dx, dy) at [dx + H - 1, dy + W - 1], -1 outside the candidates.  The child of (s, dx, dy): the grid
+    with the object's h x w box replaced by pos(flip_s(T)), T = the tile Copy + Paste leave there — the source rectangle R, the box
+    moved by (dx, dy), as it is (blank) or its positive cells over the box's own old cells (not blank) —, pos(v) = v if v > 0 else 0:
+    what CopyO on R + Paste at the box's corner + Flip of the box leave; R lies inside grid_dim, dx = 0 in slot H, dy = 0 in slot V;
+    ties go to the smaller |dx| + |dy|, then the smaller dx, then the smaller dy.  No candidate: (0, 0, 0, 0); an empty object: (0,
+    0, base correct, 1)."""
+    grid, answer = np.asarray(grid).astype(np.int8), np.asarray(answer).astype(np.int8)
+    H, W = grid.shape
+    gh, gw = min(int(grid_dim[0]), H), min(int(grid_dim[1]), W)
+    ah, aw = min(int(answer_dim[0]), H), min(int(answer_dim[1]), W)
+    mh, mw = min(gh, ah), min(gw, aw)
+    D = 2 * (H + W) if max_dist is None else int(max_dist)
+    total = mh * mw + (abs(ah * aw - gh * gw) if (gh <= ah) == (gw <= aw) else abs(gh - ah) * mw + abs(gw - aw) * mh)
+    base = (int((grid[:mh, :mw] == answer[:mh, :mw]).sum()), total)
+    masks = np.asarray(masks).reshape(-1, H, W)
+    n = masks.shape[0]
+    mirror = np.zeros((n, 3, 4), np.int32)
+    table = np.full((n, 3, 2 * H - 1, 2 * W - 1), -1, np.int32)
+    for k in range(n):
+        B = np.zeros((H, W), bool)
+        B[:gh, :gw] = masks[k, :gh, :gw] != 0
+        bx, by = np.nonzero(B)
+        for s in range(3):
+            if not (int(mirrors) >> s) & 1:
+                continue
+            if not len(bx):
+                mirror[k, s] = (0, 0, base[0], 1)
+                continue
+            x0, x1, y0, y1 = int(bx.min()), int(bx.max()), int(by.min()), int(by.max())
+            h, w = x1 - x0 + 1, y1 - y0 + 1
+            old = grid[x0:x1 + 1, y0:y1 + 1]
+            best = None
+            for sx in ((x0,) if s == 0 else range(0, gh - h + 1)):
+                for sy in ((y0,) if s == 1 else range(0, gw - w + 1)):
+                    dx, dy = sx - x0, sy - y0
+                    if abs(dx) + abs(dy) > D:
+                        continue
+                    tile = grid[sx:sx + h, sy:sy + w]
+                    if not blank:
+                        tile = np.where(tile > 0, tile, old)
+                    tile = _flipped(tile, s)
+                    child = grid.copy()
+                    child[x0:x1 + 1, y0:y1 + 1] = np.where(tile > 0, tile, 0)
+                    c = int((child[:mh, :mw] == answer[:mh, :mw]).sum())
+                    table[k, s, dx + H - 1, dy + W - 1] = c
+                    key = (-c, abs(dx) + abs(dy), dx, dy)
+                    if best is None or key < best:
+                        best = key
+            if best is not None:
+                mirror[k, s] = (best[2], best[3], -best[0], 1)
+    return (mirror, base, table) if full else (mirror, base)
+
+
+def mirror_macros(objs, mirrors, copy_op, paste_op, flip_ops, H, W):
+    """The best mirror image of every object's box (`ARCVecEnv.mirror` -> Mirrors) as ONE macro per object: {"bits": uint8 [M, C, 4,
+    128], "operation": int32 [M, C, 4], "length": int32 [M, C]}.  Step 0 is the source rectangle R — the object's box (objs.box) moved
+    by (dx, dy) — with copy_op (CopyO), step 1 the one-bit row of the box's corner (x0, y0) with paste_op, step 2 the box's rectangle
+    with FlipH (slots H and POINT) or FlipV (slot V), step 3 (slot POINT only) FlipV on the zero mask, which continues the active
+    object (object.py:102-107): lengths 3, 3, 4.  flip_ops = (FlipH index, FlipV index), -1 where the table has none; H, W = the
+    plane's size.  Per object the best valid slot that has its ops: more correct, then fewer steps, then the lower slot.  Slots with
+    k >= count, no valid slot or correct <= base[0] (the mirror gains nothing) get operation -1 at step 0 and length 1: one
+    ARCLE_ST_BAD_OP child, dropped by beam_search.  Built on the device with `pack_bits`: no host synchronisation."""
+    dev = objs.box.device
+    M, C = int(objs.box.shape[0]), int(objs.box.shape[1])
+    fh, fv = int(flip_ops[0]), int(flip_ops[1])
+    has = torch.as_tensor([fh >= 0, fv >= 0, fh >= 0 and fv >= 0], device=dev).reshape(1, 1, 3)
+    steps = torch.as_tensor([3, 3, 4], dtype=torch.int64, device=dev).reshape(1, 1, 3)
+    usable = (mirrors.valid != 0) & has
+    score = mirrors.correct.to(torch.int64) * 64 - steps * 8 - torch.arange(3, device=dev).reshape(1, 1, 3)
+    score = torch.where(usable, score, torch.full((), -1, dtype=torch.int64, device=dev))
+    pick = score.argmax(-1, keepdim=True)
+    dx, dy = mirrors.dx.gather(-1, pick).reshape(M, C).to(torch.int64), mirrors.dy.gather(-1, pick).reshape(M, C).to(torch.int64)
+    correct = mirrors.correct.gather(-1, pick).reshape(M, C)
+    pick = pick.reshape(M, C)
+    there = torch.arange(C, device=dev).reshape(1, C) < objs.count.reshape(M, 1)
+    ok = there & usable.any(-1) & (correct > mirrors.base[:, 0].reshape(M, 1))
+    x0, y0, x1, y1 = (objs.box[..., i].to(torch.int64) for i in range(4))
+    last = pick == 2
+    corner = _rect_bits(x0, x0, y0, y0, H, W)
+    bits = torch.stack([_rect_bits(x0 + dx, x1 + dx, y0 + dy, y1 + dy, H, W), corner, _rect_bits(x0, x1, y0, y1, H, W), torch.zeros_like(corner)], 2)
+    bits = torch.where(ok.reshape(M, C, 1, 1), bits, torch.zeros((), dtype=torch.uint8, device=dev))
+    minus = torch.full((M, C), -1, dtype=torch.int32, device=dev)
+    flip = torch.where(pick == 1, fv, fh).to(torch.int32)
+    op = torch.stack([torch.full((M, C), int(copy_op), dtype=torch.int32, device=dev), torch.full((M, C), int(paste_op), dtype=torch.int32, device=dev),
+                      flip, torch.where(last, torch.full((), fv, dtype=torch.int32, device=dev), minus)], 2)
+    op = torch.where(ok.reshape(M, C, 1), op, minus.reshape(M, C, 1))
+    length = torch.where(ok, torch.where(last, 4, 3), 1).to(torch.int32)
+    return {"bits": bits.contiguous(), "operation": op.to(torch.int32).contiguous(), "length": length.contiguous()}
+
+
+def propose_mirrors(copy_op, paste_op, flip_ops, box_ops=(), seed_ops=(), max_dist=None, max_components=16, skip_color=0, any_color=False,
+                    diagonal=False, blank=True):
+    """A `propose` for beam_search that answers "what belongs here by symmetry?": at every depth the objects of each frontier state's
+    grid (`venv.objects` / `venv.components` with their bit rows), first the singles of `object_actions(masks=True)` — box_ops on the
+    objects' exact cells, seed_ops on their seeds — as macros of length 1, then for every object ONE macro of three or four steps: copy_op
+    (CopyO) on the rectangle whose mirror image fits the object's box best, paste_op at the box's corner, the Flip(s) of the box
+    (`venv.mirror`, one launch; `mirror_macros`), K = C * (len(box_ops) + len(seed_ops) + 1), T = 4.  flip_ops = (FlipH index, FlipV
+    index), -1 where the table has none: only the symmetries whose ops the table has are asked for.  blank must say what paste_op does
+    in the caller's table (True: paste_blank, both default tables).  With skip_color = 0 the holes of a pattern are NOT objects: pass
+    skip_color = -1 (and any_color = False) to get the zero-coloured components.  It looks at the answer of each row's env, so it
+    carries `wants_src = True` and beam_search calls it with (venv, rows, src_env)."""
+    copy_op, paste_op, flip_ops = int(copy_op), int(paste_op), tuple(int(o) for o in flip_ops)
+    box_ops, seed_ops = list(box_ops), list(seed_ops)
+    assert len(flip_ops) == 2 and any(o >= 0 for o in flip_ops), "flip_ops: (FlipH index, FlipV index), at least one of them >= 0"
+    want = (MIRROR_H if flip_ops[0] >= 0 else 0) | (MIRROR_V if flip_ops[1] >= 0 else 0) | (MIRROR_POINT if min(flip_ops) >= 0 else 0)
+    T = 4
+
+    def propose(venv, rows, src_env=None):
+        if any_color or diagonal:
+            objs = venv.objects(rows, max_components=max_components, skip_color=skip_color, any_color=any_color, diagonal=diagonal, bits=True)
+        else:
+            objs = venv.components(rows, max_components=max_components, skip_color=skip_color, bits=True)
+        mm = mirror_macros(objs, venv.mirror(rows, objs, src_env, max_dist, want, blank), copy_op, paste_op, flip_ops, venv.H, venv.W)
+        if not box_ops and not seed_ops:
+            return mm
+        single = object_actions(objs, box_ops, seed_ops, masks=True)
+        M, K1 = (int(v) for v in single["operation"].shape)
+        dev = single["bits"].device
+        b1 = torch.zeros((M, K1, T, int(single["bits"].shape[-1])), dtype=torch.uint8, device=dev)
+        b1[:, :, 0] = single["bits"]
+        o1 = torch.full((M, K1, T), -1, dtype=torch.int32, device=dev)
+        o1[:, :, 0] = single["operation"]
+        return {"bits": torch.cat([b1, mm["bits"]], 1).contiguous(), "operation": torch.cat([o1, mm["operation"]], 1).contiguous(),
+                "length": torch.cat([torch.ones((M, K1), dtype=torch.int32, device=dev), mm["length"]], 1).contiguous()}
+    propose.wants_src = True
+    return propose

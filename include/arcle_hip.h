@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ARCLE_ABI_VERSION 16
+#define ARCLE_ABI_VERSION 17
 #define ARCLE_MAX_OPS 64
 #define ARCLE_MAX_CELLS 1024 /* H*W <= 1024: one 64-lane wavefront x 16 cells holds a plane (the one-wavefront-per-env kernels);
                                 larger planes (H, W <= 127) are served by the workgroup-per-env kernels — see "Grids beyond
@@ -719,6 +719,36 @@ int arcle_align_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t
 int arcle_ray_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, const int32_t* count,
                    const uint8_t* bits, const int32_t* src_env, const uint8_t* sets, int32_t n_sets, int32_t free_color,
                    int32_t through, int32_t* ray, int32_t* best, uint8_t* best_bits, int32_t* base, void* stream);
+/* Each object's box filled from its MIRROR IMAGE (ABI 17): for object k of row m — a bit row as for arcle_place_rows — and each symmetry
+ * asked for, the source rectangle whose flipped copy, written over the object's box, leaves the most correct cells: the repair of a
+ * symmetric pattern with a hole punched out.  It is what the step sequence CopyO on R, Paste at the box's corner, Flip of the box leaves.
+ * rows, stride, count, bits, src_env, base and stream as for arcle_turn_rows.
+ *   mirrors       the set of symmetries asked for, ARCLE_MIRROR_* bits
+ *   blank         what the table's Paste does: 1 = the clip's whole rectangle is written (paste_blank: both default tables), 0 = its
+ *                 positive cells only
+ *   mirror        int32 [n_rows][max_comp][3][4] = dx, dy, correct, valid; slot s is bit s of `mirrors`.  Slots of symmetries not in
+ *                 `mirrors`, and of objects k >= count, are not written
+ * G, (gh, gw), A, (ah, aw), (mh, mw) and B as for arcle_place_rows; (x0, y0, x1, y1) B's inclusive box of h x w cells.  A candidate of
+ * slot s is a source rectangle R of h x w cells with its corner at (x0 + dx, y0 + dy), wholly inside grid_dim, |dx| + |dy| <= max_dist;
+ * dx = 0 in slot H, dy = 0 in slot V, both free in slot POINT.  R may overlap the box, and dx = dy = 0 — the box flipped where it stands
+ * — is always a candidate.  Let T be the h x w tile that Copy + Paste leave in the box: with blank = 1, T = G[R]; with blank = 0, T =
+ * G[R] where G[R] > 0 and the box's own old cell elsewhere.  The child G'(s, dx, dy) is G with the box replaced by pos(flip_s(T)), flip_s
+ * = np.fliplr (H), np.flipud (V) or both (POINT), pos(v) = v if v > 0 else 0: the Flip lifts the whole rectangle as an object and writes
+ * back its positive cells only (object.py:60-138, 265-276, 291-348).  Nothing outside the box changes.  correct counts the cells of [0,
+ * mh) x [0, mw) where G' equals A; the total does not change.  Per slot the best candidate maximises correct; ties go to the smaller |dx|
+ * + |dy|, then the smaller dx, then the smaller dy: (dx, dy, correct, 1).  A slot without a candidate: (0, 0, 0, 0).  An empty B:
+ * (0, 0, base correct, 1) in every slot asked for.  A row whose src_env names no env gets base = (0, 0) and zeros.
+ * Out of scope: the diagonal symmetries (Flip D0 / D1 leave object_dim unswapped for non-square boxes, and the default tables carry
+ * neither op), the input plane as a source (CopyI), handles of more than ARCLE_MAX_CELLS cells.
+ * No side effects; allocates nothing: may be captured.  One wavefront per row.  Refusals, nothing written: those of arcle_place_rows,
+ * mirrors == 0 or a bit above ARCLE_MIRROR_POINT, blank outside {0, 1}: ARCLE_ERR_ARG; more than ARCLE_MAX_CELLS cells per plane, or an
+ * env kind without an answer plane: ARCLE_ERR_CONFIG. */
+#define ARCLE_MIRROR_H 1u     /* columns mirrored: what gen_flip("H") (np.fliplr) does to the pasted box */
+#define ARCLE_MIRROR_V 2u     /* rows mirrored: gen_flip("V") (np.flipud) */
+#define ARCLE_MIRROR_POINT 4u /* both: the point reflection (= a half turn) */
+int arcle_mirror_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, const int32_t* count,
+                      const uint8_t* bits, const int32_t* src_env, int32_t max_dist, uint32_t mirrors, int32_t blank, int32_t* mirror,
+                      int32_t* base, void* stream);
 /* One state plane as a dense [n_envs][H*W] int8 array (device or pinned host memory), a strided copy on the stream: the
  * get_state()/set_state() of single keys of the reference's state dict. */
 int arcle_get_plane(arcle_env* env, int plane, int8_t* dst, void* stream);
