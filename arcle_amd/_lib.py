@@ -13,10 +13,10 @@ LIB_PATH = os.environ.get("ARCLE_HIP_LIB") or os.path.join(_CSRC, "libarcle_hip.
 # two translation units: the one-wavefront-per-env kernels + the C ABI (arcle_hip.hip <- arcle_wave.h) and the workgroup-per-env kernels
 # for grids of more than 1024 cells (arcle_big.hip <- arcle_big.h); arcle_big_params.h is shared
 UNITS = [os.path.join(_CSRC, "arcle_hip.hip"), os.path.join(_CSRC, "arcle_big.hip")]
-SOURCES = UNITS + [os.path.join(_CSRC, "arcle_wave.h"), os.path.join(_CSRC, "arcle_group.h"), os.path.join(_CSRC, "arcle_search.h"), os.path.join(_CSRC, "arcle_components.h"), os.path.join(_CSRC, "arcle_objects.h"), os.path.join(_CSRC, "arcle_place.h"), os.path.join(_CSRC, "arcle_stamp.h"), os.path.join(_CSRC, "arcle_turn.h"), os.path.join(_CSRC, "arcle_align.h"), os.path.join(_CSRC, "arcle_ray.h"), os.path.join(_CSRC, "arcle_mirror.h"), os.path.join(_CSRC, "arcle_big.h"), os.path.join(_CSRC, "arcle_big_params.h"),
+SOURCES = UNITS + [os.path.join(_CSRC, "arcle_wave.h"), os.path.join(_CSRC, "arcle_group.h"), os.path.join(_CSRC, "arcle_search.h"), os.path.join(_CSRC, "arcle_components.h"), os.path.join(_CSRC, "arcle_objects.h"), os.path.join(_CSRC, "arcle_place.h"), os.path.join(_CSRC, "arcle_stamp.h"), os.path.join(_CSRC, "arcle_turn.h"), os.path.join(_CSRC, "arcle_align.h"), os.path.join(_CSRC, "arcle_ray.h"), os.path.join(_CSRC, "arcle_mirror.h"), os.path.join(_CSRC, "arcle_region.h"), os.path.join(_CSRC, "arcle_big.h"), os.path.join(_CSRC, "arcle_big_params.h"),
                    os.path.join(_CSRC, "..", "..", "include", "arcle_hip.h")]
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 N_PLANES = 8
 MAX_OPS = 64
 BITS_STRIDE = 128  # bytes between envs of a bit-packed mask array (ARCLE_MAX_CELLS / 8)
@@ -24,6 +24,7 @@ OBJ_ANY_COLOR, OBJ_DIAG = 1, 2  # ARCLE_OBJ_*: the mode bits of arcle_objects_ro
 TURN_ROT90, TURN_ROT180, TURN_ROT270, TURN_FLIP_H, TURN_FLIP_V = 1, 2, 4, 8, 16  # ARCLE_TURN_*: the turns of arcle_turn_rows
 ALIGN_GRID, ALIGN_INPUT = 1, 2  # ARCLE_ALIGN_*: the sources of arcle_align_rows
 MIRROR_H, MIRROR_V, MIRROR_POINT = 1, 2, 4  # ARCLE_MIRROR_*: the symmetries of arcle_mirror_rows
+REGION_NONE, REGION_HALO4, REGION_HALO8, REGION_BOX_REST, REGION_BOX_FRAME, REGION_INSIDE, REGION_BOX, REGION_SELF = range(8)  # ARCLE_REGION_*: the codes of arcle_region_rows
 RAY_N, RAY_S, RAY_W, RAY_E, RAY_NW, RAY_NE, RAY_SW, RAY_SE = 1, 2, 4, 8, 16, 32, 64, 128  # ARCLE_RAY_*: the directions of arcle_ray_rows
 INGRESS = {"mask": 0, "bbox": 1, "point": 2, "bbox5": 3, "bits": 4}  # enum arcle_ingress
 EXPORTS = ["arcle_abi_version", "arcle_create", "arcle_destroy", "arcle_get_buffers", "arcle_set_op_table",
@@ -33,7 +34,7 @@ EXPORTS = ["arcle_abi_version", "arcle_create", "arcle_destroy", "arcle_get_buff
            "arcle_packed_obs_size", "arcle_pack_obs", "arcle_set_packed_output", "arcle_set_sampler", "arcle_reset_sampled",
            "arcle_reset_from_table_aug", "arcle_set_dense_output", "arcle_invalidate", "arcle_flat_obs_size", "arcle_flatten_obs",
            "arcle_set_flat_output", "arcle_set_flat_output_ex", "arcle_set_flat_seq", "arcle_get_state_rows", "arcle_set_state_rows",
-           "arcle_transition_rows", "arcle_hash_rows", "arcle_expand_rows", "arcle_expand_macros", "arcle_components_rows", "arcle_objects_rows", "arcle_place_rows", "arcle_stamp_rows", "arcle_turn_rows", "arcle_align_rows", "arcle_ray_rows", "arcle_mirror_rows", "arcle_get_plane", "arcle_set_plane", "arcle_get_status",
+           "arcle_transition_rows", "arcle_hash_rows", "arcle_expand_rows", "arcle_expand_macros", "arcle_components_rows", "arcle_objects_rows", "arcle_place_rows", "arcle_stamp_rows", "arcle_turn_rows", "arcle_align_rows", "arcle_ray_rows", "arcle_mirror_rows", "arcle_region_rows", "arcle_get_plane", "arcle_set_plane", "arcle_get_status",
            "arcle_enable_accounting", "arcle_get_accounting", "arcle_get_accounting_ex", "arcle_last_error"]
 
 
@@ -153,6 +154,8 @@ def load(path, abi_version=None):
         L.arcle_ray_rows.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
     if abi_version is not None or hasattr(L, "arcle_mirror_rows"):  # (likewise)
         L.arcle_mirror_rows.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, i32, ctypes.c_uint32, i32, vp, vp, vp]
+    if abi_version is not None or hasattr(L, "arcle_region_rows"):  # (likewise)
+        L.arcle_region_rows.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
     L.arcle_get_plane.argtypes = [vp, ctypes.c_int, vp, vp]
     L.arcle_set_plane.argtypes = [vp, ctypes.c_int, vp, vp]
     L.arcle_get_accounting_ex.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),

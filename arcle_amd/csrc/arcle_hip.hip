@@ -222,6 +222,7 @@ ARCLE_DEV void touch_args(const void* a, const void* b) { asm volatile("" ::"s"(
 #include "arcle_align.h"       // the offset at which the grid or the input best fits the answer's canvas (arcle_align_rows)
 #include "arcle_ray.h"         // the lines each object casts toward the answer (arcle_ray_rows)
 #include "arcle_mirror.h"      // each object's box filled from its mirror image (arcle_mirror_rows)
+#include "arcle_region.h"      // the cells around and inside each object (arcle_region_rows)
 #include "arcle_big_params.h"  // grids beyond ARCLE_MAX_CELLS: one workgroup per env (arcle_big.hip)
 
 using arcle::StepParams;
@@ -568,6 +569,14 @@ __global__ __launch_bounds__(64 * COMP_WAVES_PER_WG) void arcle_mirror_kernel(co
   const int row = wave_of_launch(COMP_WAVES_PER_WG);
   if (row >= x.p.n_envs) return;
   arcle::wave_mirror_row<FW>(x, nullptr, nullptr, row, (int)(threadIdx.x & 63));
+}
+
+// arcle_region_rows: likewise
+template <int FW, bool FLAT>
+__global__ __launch_bounds__(64 * COMP_WAVES_PER_WG) void arcle_region_kernel(const arcle::RegionParams x) {
+  const int row = wave_of_launch(COMP_WAVES_PER_WG);
+  if (row >= x.p.n_envs) return;
+  arcle::wave_region_row<FW, FLAT>(x, nullptr, nullptr, row, (int)(threadIdx.x & 63));
 }
 
 __global__ __launch_bounds__(64 * WAVES_PER_WG) void arcle_reset_kernel(const StepParams p) {
@@ -2529,6 +2538,55 @@ extern "C" int arcle_mirror_rows(arcle_env* e, int32_t n_rows, const int8_t* row
   const dim3 g = grid_for(n_rows, COMP_WAVES_PER_WG), b(64 * COMP_WAVES_PER_WG);
   if (width_class(e->base) != arcle::FW_GENERIC) hipLaunchKernelGGL(arcle_mirror_kernel<arcle::FW_FAST>, g, b, 0, (hipStream_t)stream, x);
   else hipLaunchKernelGGL(arcle_mirror_kernel<arcle::FW_GENERIC>, g, b, 0, (hipStream_t)stream, x);
+  HIP_TRY(e, hipGetLastError());
+  return ARCLE_OK;
+}
+
+// the regions of every object of every row and their best colours (arcle_region.h): reads what arcle_ray_rows reads with the region
+// codes in the place of the direction sets, writes the caller's arrays — nothing of the handle is written.  `kinds` is device memory
+// read when the launch runs, so its codes cannot be checked here: the kernel takes a code above 7 as the empty region
+extern "C" int arcle_region_rows(arcle_env* e, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, const int32_t* count,
+                                 const uint8_t* bits, const int32_t* src_env, const uint8_t* kinds, int32_t n_kinds, int32_t free_color,
+                                 int32_t through, int32_t* region, int32_t* best, uint8_t* best_bits, int32_t* base, void* stream) {
+  if (!e || !bits || !kinds || !region || !best) return ARCLE_ERR_ARG;
+  if (n_rows <= 0) return fail(e, ARCLE_ERR_ARG, "n_rows must be positive");
+  if (e->big) return fail(e, ARCLE_ERR_CONFIG, "arcle_region_rows: handles of at most 1024 cells per plane (ARCLE_MAX_CELLS)");
+  if (!e->bufs.plane[ARCLE_PL_ANSWER]) return fail(e, ARCLE_ERR_CONFIG, "arcle_region_rows needs the answer plane");
+  if (max_comp < 1 || max_comp > ARCLE_MAX_CELLS) return fail(e, ARCLE_ERR_ARG, "arcle_region_rows: max_comp in [1, ARCLE_MAX_CELLS]");
+  if (n_kinds < 1 || n_kinds > arcle::REGION_MAX_KINDS) return fail(e, ARCLE_ERR_ARG, "arcle_region_rows: n_kinds in [1, 16]");
+  if (through != 0 && through != 1) return fail(e, ARCLE_ERR_ARG, "arcle_region_rows: through is 0 or 1");
+  if (free_color < -128 || free_color > 127) return fail(e, ARCLE_ERR_ARG, "arcle_region_rows: free_color is an int8");
+  if ((uintptr_t)bits & 1u) return fail(e, ARCLE_ERR_ARG, "arcle_region_rows: bit rows must be 2-byte aligned");
+  if ((uintptr_t)best_bits & 1u) return fail(e, ARCLE_ERR_ARG, "arcle_region_rows: best_bits must be 2-byte aligned");
+  if (rows) {
+    if (int rc = check_rows(e, rows, stride, 0)) return rc;
+  } else if (n_rows > e->cfg.n_envs) {
+    return fail(e, ARCLE_ERR_ARG, "arcle_region_rows: rows == NULL takes the resident envs (n_rows <= n_envs)");
+  }
+  DeviceGuard guard(e->device);
+  arcle::RegionParams x = {};
+  x.p = e->base;
+  x.p.n_resident = x.p.n_envs;
+  x.p.n_envs = n_rows;
+  x.p.rows_in = rows;
+  x.p.rows_in_stride = rows ? stride : 0;
+  x.max_comp = max_comp;
+  x.n_kinds = n_kinds;
+  x.count = count;
+  x.bits = bits;
+  x.src_env = src_env;
+  x.kinds = kinds;
+  x.region = region;
+  x.best = best;
+  x.best_bits = best_bits;
+  x.base = base;
+  x.free_color = free_color;
+  x.through = through;
+  const dim3 g = grid_for(n_rows, COMP_WAVES_PER_WG), b(64 * COMP_WAVES_PER_WG);
+  // (the row board serves W <= 32 and H <= 64, the flat board every other shape: one instantiation each)
+  if (width_class(e->base) != arcle::FW_GENERIC) hipLaunchKernelGGL((arcle_region_kernel<arcle::FW_FAST, false>), g, b, 0, (hipStream_t)stream, x);
+  else if (e->base.W <= 32 && e->base.H <= 64) hipLaunchKernelGGL((arcle_region_kernel<arcle::FW_GENERIC, false>), g, b, 0, (hipStream_t)stream, x);
+  else hipLaunchKernelGGL((arcle_region_kernel<arcle::FW_GENERIC, true>), g, b, 0, (hipStream_t)stream, x);
   HIP_TRY(e, hipGetLastError());
   return ARCLE_OK;
 }

@@ -913,6 +913,44 @@ class EnvBatch:
                                           int(bool(through)), _ptr(ray), _ptr(best), _ptr(bbits), _ptr(base), self._stream()), "arcle_ray_rows")
         return out
 
+    def region_rows(self, rows, count, bits, kinds, free_color=0, through=False, src_env=None, out=None, best_bits=True):
+        """The cells around and inside each object of every state row (arcle_region_rows): rows, count, bits and src_env as for
+        `place_rows`; kinds uint8 [S] on the device, 1 <= S <= 16 = one region code per candidate (_lib.REGION_*: 0 none, 1 HALO4,
+        2 HALO8, 3 BOX_REST, 4 BOX_FRAME, 5 INSIDE, 6 BOX, 7 SELF; the array is read on the device when the launch runs, so a code
+        above 7 is not refused: it counts as 0, the empty candidate); free_color = the byte (as int8) a cell outside the object must
+        hold to be painted; through = True: every cell of the region is.  Returns (region int32 [M, C, S, 4] = color, correct, cells,
+        right; best int32 [M, C, 4] = index, color, correct, cells; best_bits uint8 [M, C, 128] or None; base int32 [M, 2] = the
+        dense pair of the row's own grid): per object and candidate the cells of the region, the colour c in 0..9 for which ONE
+        `Color c` step on them leaves the most correct cells (ties: the smaller c), that number and the cells of the answer the step
+        gets right; per object the candidate with the most correct (then the fewest cells, then the lowest index; index = -1: every
+        candidate is empty) and its cells as a bit row, the "bits" selection of `expand_rows` / `transition_rows`.  Entries k >=
+        count are not written; an empty candidate gives (0, base correct, 0, 0).  The definition: include/arcle_hip.h; its NumPy
+        mirror: arcle_amd.search.region_numpy.  out: the four of a previous call with the same shapes (captured graphs; `kinds` is
+        read when the launch runs).  Nothing of the batch is touched."""
+        assert bits.dtype == torch.uint8 and bits.dim() == 3 and bits.shape[2] == _lib.BITS_STRIDE and bits.is_contiguous()
+        assert kinds.dtype == torch.uint8 and kinds.dim() == 1 and kinds.is_contiguous() and kinds.device == bits.device
+        C, S = int(bits.shape[1]), int(kinds.shape[0])
+        if rows is None:
+            M, ptr, stride = int(bits.shape[0]), None, 0
+        else:
+            assert rows.dtype == torch.int8 and rows.dim() == 2 and rows.stride(1) == 1
+            M, ptr, stride = int(rows.shape[0]), _ptr(rows), rows.stride(0)
+        assert int(bits.shape[0]) == M
+        assert count is None or (count.dtype == torch.int32 and tuple(count.shape) == (M, 2) and count.is_contiguous())
+        assert src_env is None or (src_env.dtype == torch.int32 and tuple(src_env.shape) == (M,) and src_env.is_contiguous())
+        if out is None:
+            out = (torch.zeros((M, C, S, 4), dtype=torch.int32, device=self.device), torch.zeros((M, C, 4), dtype=torch.int32, device=self.device),
+                   torch.zeros((M, C, _lib.BITS_STRIDE), dtype=torch.uint8, device=self.device) if best_bits else None,
+                   torch.zeros((M, 2), dtype=torch.int32, device=self.device))
+        region, best, bbits, base = out
+        assert region.dtype == torch.int32 and tuple(region.shape) == (M, C, S, 4) and region.is_contiguous()
+        assert best.dtype == torch.int32 and tuple(best.shape) == (M, C, 4) and best.is_contiguous()
+        assert bbits is None or (bbits.dtype == torch.uint8 and tuple(bbits.shape) == (M, C, _lib.BITS_STRIDE) and bbits.is_contiguous())
+        assert base is None or (base.dtype == torch.int32 and tuple(base.shape) == (M, 2) and base.is_contiguous())
+        self._check(self.L.arcle_region_rows(self._h, M, ptr, stride, C, _ptr(count), _ptr(bits), _ptr(src_env), _ptr(kinds), S, int(free_color),
+                                             int(bool(through)), _ptr(region), _ptr(best), _ptr(bbits), _ptr(base), self._stream()), "arcle_region_rows")
+        return out
+
     def get_plane(self, name, out=None):
         """One key of the state dict as a dense [N, H, W] int8 array (device tensor, or a pinned host tensor passed as `out`):
         arcle_get_plane, a strided copy on the current stream."""

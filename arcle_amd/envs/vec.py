@@ -48,6 +48,9 @@ Alignments = collections.namedtuple("Alignments", "ox oy correct total src_dim a
 # rays' cells should paint, the correct cells it leaves, the rays' cells, the cells it gets right), of one int32 [M, C, 4] buffer (the
 # best set of every object, its colour, correct cells and cells), that set's cells as bit rows and the dense pair of every row's own grid
 Rays = collections.namedtuple("Rays", "color correct cells right best_set best_color best_correct best_cells best_bits base")
+# what ARCVecEnv.regions returns: the same arrangement for the regions of arcle_region_rows (halo, box, frame, inside ...); best_kind is
+# the INDEX of the best candidate in the list of kinds asked for
+Regions = collections.namedtuple("Regions", "color correct cells right best_kind best_color best_correct best_cells best_bits base")
 
 
 def _table_of(env_cls, **ctor_kw):
@@ -793,6 +796,29 @@ class ARCVecEnv:
             sets.to(device=self.device, dtype=torch.uint8).contiguous()
         ray, best, bbits, base = self.batch.ray_rows(rows, count, objs.bits.contiguous(), sets, free_color, through, src_env, bits)
         return Rays(ray[..., 0], ray[..., 1], ray[..., 2], ray[..., 3], best[..., 0], best[..., 1], best[..., 2], best[..., 3], bbits, base)
+
+    def regions(self, rows, objs, kinds=None, free_color=0, through=False, bits=True, src_env=None):
+        """The cells around and inside each object (arcle_region_rows, one launch; no step is run): objs, rows and src_env as for
+        `place`; kinds = the candidates, one region code each (0 none, 1 HALO4, 2 HALO8, 3 BOX_REST, 4 BOX_FRAME, 5 INSIDE, 6 BOX,
+        7 SELF; at most 16; None: `search.REGION_KINDS` = 1 .. 7); free_color = the byte a cell outside the object must hold to be
+        painted (0: the background); through = True: every cell of the region is painted.  Returns a Regions of device tensors:
+        color, correct, cells, right [M, C, S] = per object and candidate the colour c for which ONE `Color c` step on the region's
+        cells leaves the most correct cells, that number, the region's cells and the cells the step gets right; best_kind,
+        best_color, best_correct, best_cells [M, C] = the candidate (its INDEX in kinds) with the most correct (then the fewest
+        cells, then the lowest index; -1: every candidate is empty); best_bits [M, C, 128] = its cells as a bit row, a "bits"
+        selection for `expand` / `transition` (None with bits=False); base [M, 2] = the dense pair of the row's own grid.  Entries
+        k >= count are zero.  `search.region_actions` turns it into one Color step per object.  This env's state is not touched."""
+        assert objs.bits is not None, "regions needs the objects' bit rows (bits=True)"
+        count = torch.stack([objs.count, objs.left], 1).to(torch.int32).contiguous()
+        if src_env is not None:
+            src_env = src_env.to(device=self.device, dtype=torch.int32).contiguous()
+        if kinds is None:
+            from .. import search
+            kinds = search.REGION_KINDS
+        kinds = torch.as_tensor([int(s) for s in kinds], dtype=torch.uint8, device=self.device) if not torch.is_tensor(kinds) else \
+            kinds.to(device=self.device, dtype=torch.uint8).contiguous()
+        reg, best, bbits, base = self.batch.region_rows(rows, count, objs.bits.contiguous(), kinds, free_color, through, src_env, best_bits=bits)
+        return Regions(reg[..., 0], reg[..., 1], reg[..., 2], reg[..., 3], best[..., 0], best[..., 1], best[..., 2], best[..., 3], bbits, base)
 
     def autotune(self, payload, operation=None, form="bbox"):
         """Times every launch plan the library has for this env's steps (self-ordering or not, the cache policies of the speculative grid

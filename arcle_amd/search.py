@@ -6,7 +6,8 @@ object best fits the answer (`place_numpy`: the host mirror of arcle_place_rows;
 best translation of every object as ONE Move macro), and where a COPY of each object best fits it (`stamp_numpy`: the host mirror of
 arcle_stamp_rows; `stamp_macros` / `propose_stamps`: the best paste position of every object as ONE CopyO + Paste macro), and the
 lines each object casts toward the answer (`ray_numpy`: the host mirror of arcle_ray_rows; `ray_actions` / `propose_rays`: the best
-set of rays of every object as ONE Color step).
+set of rays of every object as ONE Color step), and the cells around and inside each object (`region_numpy`: the host mirror of
+arcle_region_rows; `region_actions` / `propose_regions`: the best halo, box, frame or inside of every object as ONE Color step).
 
 The hash is defined in include/arcle_hip.h (next to arcle_hash_rows) and computed on the device by arcle_amd/csrc/arcle_search.h;
 `hash_rows_numpy` restates it on the host — the same arrangement as arcle_amd/sampling.py for the device RNG — and is what the tests
@@ -1174,5 +1175,140 @@ def propose_mirrors(copy_op, paste_op, flip_ops, box_ops=(), seed_ops=(), max_di
         o1[:, :, 0] = single["operation"]
         return {"bits": torch.cat([b1, mm["bits"]], 1).contiguous(), "operation": torch.cat([o1, mm["operation"]], 1).contiguous(),
                 "length": torch.cat([torch.ones((M, K1), dtype=torch.int32, device=dev), mm["length"]], 1).contiguous()}
+    propose.wants_src = True
+    return propose
+
+
+# ---- the cells around and inside each object ----------------------------------------------------------------------------------------
+# the codes of a candidate region (ARCLE_REGION_*)
+REGION_NONE, REGION_HALO4, REGION_HALO8, REGION_BOX_REST, REGION_BOX_FRAME, REGION_INSIDE, REGION_BOX, REGION_SELF = range(8)
+# the default candidates of `ARCVecEnv.regions` / `propose_regions`
+REGION_KINDS = (1, 2, 3, 4, 5, 6, 7)
+
+
+def region_numpy(grid, grid_dim, answer, answer_dim, masks, kinds=None, free_color=0, through=False, full=False):
+    """The regions of every object of ONE grid as arcle_region_rows reports them (include/arcle_hip.h) — the host mirror and the
+    normative statement, straight from the definition and deliberately not a bit-board algorithm: neighbourhoods by array slices,
+    INSIDE by a cell-by-cell flood from the edge of grid_dim.  grid, answer int8 [H, W]; masks [n, H, W] (truthy = the object's cells;
+    cells outside grid_dim are ignored); kinds: region codes (0 none, 1 HALO4, 2 HALO8, 3 BOX_REST, 4 BOX_FRAME, 5 INSIDE, 6 BOX,
+    7 SELF; a code above 7 counts as 0; None: REGION_KINDS); free_color: the byte (as int8) a cell outside the object must hold to be
+    painted; through=True: every cell may be.  -> (region int32 [n, S, 4] = color, correct, cells, right; best int32 [n, 4] = index,
+    color, correct, cells; base (correct, total) of the grid itself); full=True adds cells bool [n, S, H, W]: every candidate's
+    selection.  With IN = the cells inside grid_dim, B = the object's cells in IN, box = B's bounding rectangle: HALO4 / HALO8 = the
+    cells of IN & ~B with a 4- / 8-neighbour in B; BOX_REST = box & ~B; BOX_FRAME = the rectangle one cell larger than box on every
+    side, minus box, clipped to IN; INSIDE = the cells of IN & ~B from which no 4-connected path through IN & ~B leads to a cell on
+    the edge of grid_dim (an edge cell is never inside); BOX = box; SELF = B; an empty B gives empty regions.  The candidate's cells
+    are R = region & (B | FREE), FREE = the cells of IN whose byte is free_color (through: IN).  color = the c in 0..9 most frequent
+    in the answer under R inside the common rectangle (ties: the smaller c), right = that frequency, correct = the correct cells of
+    the grid with R painted c.  An empty candidate: (0, base correct, 0, 0).  best: the most correct among the non-empty candidates,
+    then the fewest cells, then the lowest index; none: (-1, 0, base correct, 0)."""
+    grid, answer = np.asarray(grid).astype(np.int8), np.asarray(answer).astype(np.int8)
+    H, W = grid.shape
+    gh, gw = min(int(grid_dim[0]), H), min(int(grid_dim[1]), W)
+    ah, aw = min(int(answer_dim[0]), H), min(int(answer_dim[1]), W)
+    mh, mw = min(gh, ah), min(gw, aw)
+    total = mh * mw + (abs(ah * aw - gh * gw) if (gh <= ah) == (gw <= aw) else abs(gh - ah) * mw + abs(gw - aw) * mh)
+    base = (int((grid[:mh, :mw] == answer[:mh, :mw]).sum()), total)
+    kinds = [int(k) if 0 <= int(k) <= 7 else 0 for k in (REGION_KINDS if kinds is None else kinds)]
+    fc = (int(free_color) + 128) % 256 - 128
+    masks = np.asarray(masks).reshape(-1, H, W)
+    n, S_ = masks.shape[0], len(kinds)
+    region, best = np.zeros((n, S_, 4), np.int32), np.zeros((n, 4), np.int32)
+    cells = np.zeros((n, S_, H, W), bool)
+    IN = np.zeros((H, W), bool)
+    IN[:gh, :gw] = True
+    FREE = IN & (True if through else grid == fc)
+
+    def grown(X, diagonal):
+        out = np.zeros((H + 2, W + 2), bool)
+        for dx in (-1, 0, 1):
+            for dy in (-1, 0, 1):
+                if (dx or dy) and (diagonal or not (dx and dy)):
+                    out[1 + dx:1 + dx + H, 1 + dy:1 + dy + W] |= X
+        return out[1:-1, 1:-1]
+    for k in range(n):
+        B = np.zeros((H, W), bool)
+        B[:gh, :gw] = masks[k, :gh, :gw] != 0
+        per = np.zeros((8, H, W), bool)
+        if B.any():
+            xs, ys = np.nonzero(B)
+            x0, x1, y0, y1 = int(xs.min()), int(xs.max()), int(ys.min()), int(ys.max())
+            box = np.zeros((H, W), bool)
+            box[x0:x1 + 1, y0:y1 + 1] = True
+            outer = np.zeros((H, W), bool)
+            outer[max(x0 - 1, 0):x1 + 2, max(y0 - 1, 0):y1 + 2] = True
+            per[1], per[2] = grown(B, False) & IN & ~B, grown(B, True) & IN & ~B
+            per[3], per[4], per[6], per[7] = box & ~B, outer & ~box & IN, box, B
+            M = IN & ~B
+            out = np.zeros((H, W), bool)
+            stack = [(i, j) for i in range(gh) for j in range(gw) if M[i, j] and (i in (0, gh - 1) or j in (0, gw - 1))]
+            for i, j in stack:
+                out[i, j] = True
+            while stack:
+                i, j = stack.pop()
+                for a, b in ((i - 1, j), (i + 1, j), (i, j - 1), (i, j + 1)):
+                    if 0 <= a < gh and 0 <= b < gw and M[a, b] and not out[a, b]:
+                        out[a, b] = True
+                        stack.append((a, b))
+            per[5] = M & ~out
+        top = None
+        for s, code in enumerate(kinds):
+            R = per[code] & (B | FREE)
+            cells[k, s] = R
+            if not R.any():
+                region[k, s] = (0, base[0], 0, 0)
+                continue
+            under = answer[:mh, :mw][R[:mh, :mw]]
+            freq = [int((under == c).sum()) for c in range(10)]
+            color = int(np.argmax(freq))  # (the first maximum: the smaller c)
+            child = grid.copy()
+            child[R] = color
+            region[k, s] = (color, int((child[:mh, :mw] == answer[:mh, :mw]).sum()), int(R.sum()), freq[color])
+            key = (-int(region[k, s, 1]), int(region[k, s, 2]), s)
+            if top is None or key < top:
+                top = key
+        best[k] = (-1, 0, base[0], 0) if top is None else (top[2], region[k, top[2], 0], -top[0], top[1])
+    return (region, best, base, cells) if full else (region, best, base)
+
+
+def region_actions(objs, regions, color_ops):
+    """The best region of every object (`ARCVecEnv.regions` -> Regions, with its bit rows) as ONE single-step candidate per object:
+    {"bits": uint8 [M, C, 128] = regions.best_bits, "operation": int32 [M, C] = color_ops[best_color]} — color_ops[c] = the index of
+    `Color c` in the caller's op table, c = 0..9.  Slots with k >= count, without a candidate (best_kind < 0) or whose step would not
+    gain (best_correct <= base correct) get operation -1 and a zero bit row: an ARCLE_ST_BAD_OP child, dropped by beam_search.  Pure
+    indexing on the device: no host synchronisation."""
+    assert regions.best_bits is not None, "region_actions needs the candidates' bit rows (regions(bits=True))"
+    dev = regions.best_bits.device
+    M, C = (int(v) for v in regions.best_kind.shape)
+    ops = torch.as_tensor(list(color_ops), dtype=torch.int32, device=dev)
+    assert int(ops.numel()) == 10, "color_ops: the ten Color ops, color_ops[c] paints c"
+    there = torch.arange(C, device=dev).reshape(1, C) < objs.count.reshape(M, 1)
+    ok = there & (regions.best_kind >= 0) & (regions.best_correct > regions.base[:, 0].reshape(M, 1))
+    op = torch.where(ok, ops[regions.best_color.clamp(0, 9).to(torch.int64)], torch.full((), -1, dtype=torch.int32, device=dev))
+    bits = torch.where(ok.reshape(M, C, 1), regions.best_bits, torch.zeros((), dtype=torch.uint8, device=dev))
+    return {"bits": bits.contiguous(), "operation": op.to(torch.int32).contiguous()}
+
+
+def propose_regions(color_ops, kinds=None, free_color=0, through=False, box_ops=(), seed_ops=(), max_components=16, skip_color=0, any_color=False,
+                    diagonal=False):
+    """A `propose` for beam_search that answers "which cells around or inside this object should be painted?": at every depth the
+    objects of each frontier state's grid (`venv.objects` / `venv.components` with their bit rows), first the singles of
+    `object_actions(masks=True)` — box_ops on the objects' exact cells, seed_ops on their seeds — then for every object ONE step:
+    `Color c` on the cells of its best region (`venv.regions`, one launch; `region_actions`), K = C * (len(box_ops) + len(seed_ops) +
+    1).  color_ops[c] = the index of `Color c` in the env's op table (both default tables: range(10)); kinds, free_color, through as
+    for `ARCVecEnv.regions`.  These are single steps: beam_search takes them through `venv.expand` / `venv.transition`.  It looks at
+    the answer of each row's env, so it carries `wants_src = True` and beam_search calls it with (venv, rows, src_env)."""
+    color_ops, box_ops, seed_ops = [int(o) for o in color_ops], list(box_ops), list(seed_ops)
+
+    def propose(venv, rows, src_env=None):
+        if any_color or diagonal:
+            objs = venv.objects(rows, max_components=max_components, skip_color=skip_color, any_color=any_color, diagonal=diagonal, bits=True)
+        else:
+            objs = venv.components(rows, max_components=max_components, skip_color=skip_color, bits=True)
+        ra = region_actions(objs, venv.regions(rows, objs, kinds, free_color, through, src_env=src_env), color_ops)
+        if not box_ops and not seed_ops:
+            return ra
+        single = object_actions(objs, box_ops, seed_ops, masks=True)
+        return {"bits": torch.cat([single["bits"], ra["bits"]], 1).contiguous(), "operation": torch.cat([single["operation"], ra["operation"]], 1).contiguous()}
     propose.wants_src = True
     return propose

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ARCLE_ABI_VERSION 17
+#define ARCLE_ABI_VERSION 18
 #define ARCLE_MAX_OPS 64
 #define ARCLE_MAX_CELLS 1024 /* H*W <= 1024: one 64-lane wavefront x 16 cells holds a plane (the one-wavefront-per-env kernels);
                                 larger planes (H, W <= 127) are served by the workgroup-per-env kernels — see "Grids beyond
@@ -749,6 +749,68 @@ int arcle_ray_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t s
 int arcle_mirror_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, const int32_t* count,
                       const uint8_t* bits, const int32_t* src_env, int32_t max_dist, uint32_t mirrors, int32_t blank, int32_t* mirror,
                       int32_t* base, void* stream);
+/* The cells AROUND and INSIDE each object of a state row (ABI 18): for object k of row m — a bit row as for arcle_place_rows — and each
+ * of n_kinds kinds of region, the region's cells, the colour c for which ONE `Color c` step on exactly those cells (color.py:70-77)
+ * leaves the most correct cells, and that number, in closed form: no step is run.  A sibling of arcle_ray_rows, which draws straight
+ * lines: "outline every object", "fill the inside of every closed shape", "fill the rest of the bounding box", "a frame round the box"
+ * are one step each.
+ *   rows, stride, max_comp, count, bits, src_env, base, stream   as for arcle_place_rows
+ *   kinds         uint8 [n_kinds], 1 <= n_kinds <= 16, the same for all rows: DEVICE memory, read by the kernel when the launch runs
+ *                 (like the `sets` of arcle_ray_rows: a captured launch sees the bytes it holds at replay).  Entry s is an
+ *                 ARCLE_REGION_* code.  ARCLE_REGION_NONE is allowed and is the empty candidate.  Because the array lives on the
+ *                 device, this entry point cannot see its codes: a code above 7 is NOT refused, the kernel takes it as
+ *                 ARCLE_REGION_NONE
+ *   free_color    through = 0: the int8 byte a cell OUTSIDE the object must hold to be painted, -128 .. 127 (callers pass 0: the
+ *                 background)
+ *   through       0: the free filter applies; 1: every cell of the region is painted
+ *   region        int32 [n_rows][max_comp][n_kinds][4] = color, correct, cells, right; slots of objects k >= count are not written
+ *   best          int32 [n_rows][max_comp][4] = index (into kinds), color, correct, cells; likewise
+ *   best_bits     optional uint8 [n_rows][max_comp][arcle_mask_bits_stride()], 2-byte aligned: the best candidate's cells in the bit-row
+ *                 format of arcle_expand_rows / arcle_transition_rows (ARCLE_INGRESS_BITS); all arcle_mask_bits_stride() bytes of a
+ *                 written slot are written
+ * BOARDS.  G, (gh, gw), A, (ah, aw), (mh, mw) and B as for arcle_ray_rows: B is the cells of the bit row inside IN = [0, gh) x [0, gw)
+ * (bits outside it or at indices >= H * W are ignored).  FREE = the cells of IN whose grid byte equals free_color as int8; with through
+ * = 1, FREE = IN.  box = the bounding rectangle [x0, x1] x [y0, y1] of B, computed from B (not passed in).
+ * REGIONS.
+ *   ARCLE_REGION_NONE       empty
+ *   ARCLE_REGION_HALO4      the cells of IN & ~B with a 4-neighbour in B
+ *   ARCLE_REGION_HALO8      the cells of IN & ~B with an 8-neighbour in B
+ *   ARCLE_REGION_BOX_REST   box & ~B
+ *   ARCLE_REGION_BOX_FRAME  [x0 - 1, x1 + 1] x [y0 - 1, y1 + 1] minus box, clipped to IN
+ *   ARCLE_REGION_INSIDE     the cells of IN & ~B from which no path of 4-connected steps through IN & ~B leads to a cell on the edge
+ *                           of grid_dim (row 0 or gh - 1, column 0 or gw - 1).  An edge cell is never inside: the grid's edge does not
+ *                           close a shape.  A ring whose cells touch only diagonally does enclose: the path is 4-connected
+ *   ARCLE_REGION_BOX        box, B's cells included
+ *   ARCLE_REGION_SELF       B
+ * An empty B has no box: all its regions are empty.  Nothing lies outside IN and nothing wraps from one row or column into the next.
+ * CANDIDATES.  Candidate s of an object is R_s = region(kinds[s]) & (B | FREE): the free filter applies to the cells outside the object
+ * only.  Its step is ONE `Color c` on the selection R_s, whose child is G with R_s's cells set to c: grid_dim and the dense total do not
+ * change.  With K = the cells of the common rectangle at which G equals A,
+ *   cells   = |R_s|   (up to H * W: BOX or SELF of an object that is the whole grid)
+ *   right   = max over c in 0..9 of |{(x, y) in R_s, inside the common rectangle, A[x, y] == c}|,  color = the smallest c reaching it
+ *   correct = base correct - |R_s & K| + right      — the first number of the child's dense pair
+ * and an empty R_s gives the slot (0, base correct, 0, 0).
+ * BEST.  Among the candidates with cells > 0 the one with the most correct; ties go to fewer cells, then to the lower index:
+ * (index, color, correct, cells) and R_index in best_bits.  If every candidate is empty: (-1, 0, base correct, 0) and an all-zero bit
+ * row.  base is the dense pair of the row's own grid, as the siblings write it.  A row whose src_env names no env gets base = (0, 0) and
+ * zeros in all slots of its objects (region, best and best_bits).
+ * Out of scope: handles of more than ARCLE_MAX_CELLS cells; halos wider than one cell; the inside under 8-connected paths; regions of
+ * more than one colour (only the best c of each is reported).
+ * No side effects; allocates nothing: may be captured.  One wavefront per row.  Refusals, nothing written: those of arcle_ray_rows with
+ * kinds / n_kinds / region in the place of sets / n_sets / ray (kinds, region or best NULL, n_kinds outside [1, 16], an odd best_bits
+ * address, through outside {0, 1}, free_color outside [-128, 127]: ARCLE_ERR_ARG; more than ARCLE_MAX_CELLS cells per plane, or an env
+ * kind without an answer plane: ARCLE_ERR_CONFIG). */
+#define ARCLE_REGION_NONE 0u
+#define ARCLE_REGION_HALO4 1u
+#define ARCLE_REGION_HALO8 2u
+#define ARCLE_REGION_BOX_REST 3u
+#define ARCLE_REGION_BOX_FRAME 4u
+#define ARCLE_REGION_INSIDE 5u
+#define ARCLE_REGION_BOX 6u
+#define ARCLE_REGION_SELF 7u
+int arcle_region_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, const int32_t* count,
+                      const uint8_t* bits, const int32_t* src_env, const uint8_t* kinds, int32_t n_kinds, int32_t free_color,
+                      int32_t through, int32_t* region, int32_t* best, uint8_t* best_bits, int32_t* base, void* stream);
 /* One state plane as a dense [n_envs][H*W] int8 array (device or pinned host memory), a strided copy on the stream: the
  * get_state()/set_state() of single keys of the reference's state dict. */
 int arcle_get_plane(arcle_env* env, int plane, int8_t* dst, void* stream);
