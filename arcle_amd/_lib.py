@@ -13,8 +13,8 @@ LIB_PATH = os.environ.get("ARCLE_HIP_LIB") or os.path.join(_CSRC, "libarcle_hip.
 # two translation units: the one-wavefront-per-env kernels + the C ABI (arcle_hip.hip <- arcle_wave.h) and the workgroup-per-env kernels
 # for grids of more than 1024 cells (arcle_big.hip <- arcle_big.h); arcle_big_params.h is shared
 UNITS = [os.path.join(_CSRC, "arcle_hip.hip"), os.path.join(_CSRC, "arcle_big.hip")]
-SOURCES = UNITS + [os.path.join(_CSRC, "arcle_wave.h"), os.path.join(_CSRC, "arcle_group.h"), os.path.join(_CSRC, "arcle_search.h"), os.path.join(_CSRC, "arcle_components.h"), os.path.join(_CSRC, "arcle_objects.h"), os.path.join(_CSRC, "arcle_place.h"), os.path.join(_CSRC, "arcle_stamp.h"), os.path.join(_CSRC, "arcle_turn.h"), os.path.join(_CSRC, "arcle_align.h"), os.path.join(_CSRC, "arcle_ray.h"), os.path.join(_CSRC, "arcle_mirror.h"), os.path.join(_CSRC, "arcle_region.h"), os.path.join(_CSRC, "arcle_big.h"), os.path.join(_CSRC, "arcle_big_params.h"),
-                   os.path.join(_CSRC, "..", "..", "include", "arcle_hip.h")]
+SOURCES = UNITS + [os.path.join(_CSRC, "arcle_wave.h"), os.path.join(_CSRC, "arcle_group.h"), os.path.join(_CSRC, "arcle_search.h"), os.path.join(_CSRC, "arcle_components.h"), os.path.join(_CSRC, "arcle_objects.h"), os.path.join(_CSRC, "arcle_place.h"), os.path.join(_CSRC, "arcle_stamp.h"), os.path.join(_CSRC, "arcle_turn.h"), os.path.join(_CSRC, "arcle_align.h"), os.path.join(_CSRC, "arcle_ray.h"), os.path.join(_CSRC, "arcle_mirror.h"), os.path.join(_CSRC, "arcle_region.h"), os.path.join(_CSRC, "arcle_scale.h"), os.path.join(_CSRC, "arcle_big.h"), os.path.join(_CSRC, "arcle_big_params.h"),
+                   os.path.join(_CSRC, "..", "..", "include", "arcle_hip.h"), os.path.join(_CSRC, "..", "..", "include", "arcle_scale_rows.h")]
 
 ABI_VERSION = 18
 N_PLANES = 8
@@ -25,7 +25,11 @@ TURN_ROT90, TURN_ROT180, TURN_ROT270, TURN_FLIP_H, TURN_FLIP_V = 1, 2, 4, 8, 16 
 ALIGN_GRID, ALIGN_INPUT = 1, 2  # ARCLE_ALIGN_*: the sources of arcle_align_rows
 MIRROR_H, MIRROR_V, MIRROR_POINT = 1, 2, 4  # ARCLE_MIRROR_*: the symmetries of arcle_mirror_rows
 REGION_NONE, REGION_HALO4, REGION_HALO8, REGION_BOX_REST, REGION_BOX_FRAME, REGION_INSIDE, REGION_BOX, REGION_SELF = range(8)  # ARCLE_REGION_*: the codes of arcle_region_rows
+SCALE_ZOOM, SCALE_SHRINK, SCALE_TILE, SCALE_CANDS = 1, 2, 4, 132  # ARCLE_SCALE_*: the modes and the candidates of arcle_scale_rows
 RAY_N, RAY_S, RAY_W, RAY_E, RAY_NW, RAY_NE, RAY_SW, RAY_SE = 1, 2, 4, 8, 16, 32, 64, 128  # ARCLE_RAY_*: the directions of arcle_ray_rows
+# entry points of extension headers (include/arcle_scale_rows.h): added beside ABI 18's, which stay as EXPORTS lists them; a library
+# loaded as the current one must carry them
+EXTENSIONS = ["arcle_scale_rows"]
 INGRESS = {"mask": 0, "bbox": 1, "point": 2, "bbox5": 3, "bits": 4}  # enum arcle_ingress
 EXPORTS = ["arcle_abi_version", "arcle_create", "arcle_destroy", "arcle_get_buffers", "arcle_set_op_table",
            "arcle_can_elide_selected", "arcle_reset", "arcle_set_task_table", "arcle_reset_from_table",
@@ -156,6 +160,8 @@ def load(path, abi_version=None):
         L.arcle_mirror_rows.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, i32, ctypes.c_uint32, i32, vp, vp, vp]
     if abi_version is not None or hasattr(L, "arcle_region_rows"):  # (likewise)
         L.arcle_region_rows.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
+    if abi_version is not None or hasattr(L, "arcle_scale_rows"):  # (likewise; the scale extension: the current library must have it)
+        L.arcle_scale_rows.argtypes = [vp, i32, vp, i32, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp, vp]
     L.arcle_get_plane.argtypes = [vp, ctypes.c_int, vp, vp]
     L.arcle_set_plane.argtypes = [vp, ctypes.c_int, vp, vp]
     L.arcle_get_accounting_ex.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),

@@ -223,6 +223,7 @@ ARCLE_DEV void touch_args(const void* a, const void* b) { asm volatile("" ::"s"(
 #include "arcle_ray.h"         // the lines each object casts toward the answer (arcle_ray_rows)
 #include "arcle_mirror.h"      // each object's box filled from its mirror image (arcle_mirror_rows)
 #include "arcle_region.h"      // the cells around and inside each object (arcle_region_rows)
+#include "arcle_scale.h"       // the grid or the input zoomed, shrunk or tiled onto the answer's canvas (arcle_scale_rows)
 #include "arcle_big_params.h"  // grids beyond ARCLE_MAX_CELLS: one workgroup per env (arcle_big.hip)
 
 using arcle::StepParams;
@@ -577,6 +578,14 @@ __global__ __launch_bounds__(64 * COMP_WAVES_PER_WG) void arcle_region_kernel(co
   const int row = wave_of_launch(COMP_WAVES_PER_WG);
   if (row >= x.p.n_envs) return;
   arcle::wave_region_row<FW, FLAT>(x, nullptr, nullptr, row, (int)(threadIdx.x & 63));
+}
+
+// arcle_scale_rows: likewise
+template <int FW, bool FLAT>
+__global__ __launch_bounds__(64 * COMP_WAVES_PER_WG) void arcle_scale_kernel(const arcle::ScaleParams x) {
+  const int row = wave_of_launch(COMP_WAVES_PER_WG);
+  if (row >= x.p.n_envs) return;
+  arcle::wave_scale_row<FW, FLAT>(x, nullptr, nullptr, row, (int)(threadIdx.x & 63));
 }
 
 __global__ __launch_bounds__(64 * WAVES_PER_WG) void arcle_reset_kernel(const StepParams p) {
@@ -2587,6 +2596,46 @@ extern "C" int arcle_region_rows(arcle_env* e, int32_t n_rows, const int8_t* row
   if (width_class(e->base) != arcle::FW_GENERIC) hipLaunchKernelGGL((arcle_region_kernel<arcle::FW_FAST, false>), g, b, 0, (hipStream_t)stream, x);
   else if (e->base.W <= 32 && e->base.H <= 64) hipLaunchKernelGGL((arcle_region_kernel<arcle::FW_GENERIC, false>), g, b, 0, (hipStream_t)stream, x);
   else hipLaunchKernelGGL((arcle_region_kernel<arcle::FW_GENERIC, true>), g, b, 0, (hipStream_t)stream, x);
+  HIP_TRY(e, hipGetLastError());
+  return ARCLE_OK;
+}
+
+// the best zoom, shrink or tiling of the grid and / or the input of every row onto the answer's canvas (arcle_scale.h): reads what
+// arcle_align_rows reads, writes the caller's arrays — nothing of the handle is written
+extern "C" int arcle_scale_rows(arcle_env* e, int32_t n_rows, const int8_t* rows, int32_t stride, const int32_t* src_env, uint32_t sources,
+                                uint32_t modes, int32_t* scale, int32_t* table, uint8_t* bits, int32_t* base, void* stream) {
+  if (!e || !scale) return ARCLE_ERR_ARG;
+  if (n_rows <= 0) return fail(e, ARCLE_ERR_ARG, "n_rows must be positive");
+  if (e->big) return fail(e, ARCLE_ERR_CONFIG, "arcle_scale_rows: handles of at most 1024 cells per plane (ARCLE_MAX_CELLS)");
+  if (!e->bufs.plane[ARCLE_PL_ANSWER]) return fail(e, ARCLE_ERR_CONFIG, "arcle_scale_rows needs the answer plane");
+  if (sources == 0u || sources > (ARCLE_ALIGN_GRID | ARCLE_ALIGN_INPUT)) return fail(e, ARCLE_ERR_ARG, "arcle_scale_rows: sources is a non-empty set of ARCLE_ALIGN_* bits");
+  if (modes == 0u || modes > (ARCLE_SCALE_ZOOM | ARCLE_SCALE_SHRINK | ARCLE_SCALE_TILE)) return fail(e, ARCLE_ERR_ARG, "arcle_scale_rows: modes is a non-empty set of ARCLE_SCALE_* bits");
+  if ((uintptr_t)bits & 1u) return fail(e, ARCLE_ERR_ARG, "arcle_scale_rows: bits must be 2-byte aligned");
+  if (rows) {
+    if (int rc = check_rows(e, rows, stride, 0)) return rc;
+  } else if (n_rows > e->cfg.n_envs) {  // (with or without src_env: row m's grid is env m's)
+    return fail(e, ARCLE_ERR_ARG, "arcle_scale_rows: rows == NULL takes the resident envs (n_rows <= n_envs)");
+  }
+  static_assert(arcle::SCALE_CANDS == ARCLE_SCALE_CANDS, "the header's candidate count");
+  DeviceGuard guard(e->device);
+  arcle::ScaleParams x = {};
+  x.p = e->base;
+  x.p.n_resident = x.p.n_envs;
+  x.p.n_envs = n_rows;
+  x.p.rows_in = rows;
+  x.p.rows_in_stride = rows ? stride : 0;
+  x.sources = sources;
+  x.modes = modes;
+  x.src_env = src_env;
+  x.scale = scale;
+  x.table = table;
+  x.bits = bits;
+  x.base = base;
+  const dim3 g = grid_for(n_rows, COMP_WAVES_PER_WG), b(64 * COMP_WAVES_PER_WG);
+  // (the row board serves W <= 32 and H <= 64, the flat board every other shape: one instantiation each)
+  if (width_class(e->base) != arcle::FW_GENERIC) hipLaunchKernelGGL((arcle_scale_kernel<arcle::FW_FAST, false>), g, b, 0, (hipStream_t)stream, x);
+  else if (e->base.W <= 32 && e->base.H <= 64) hipLaunchKernelGGL((arcle_scale_kernel<arcle::FW_GENERIC, false>), g, b, 0, (hipStream_t)stream, x);
+  else hipLaunchKernelGGL((arcle_scale_kernel<arcle::FW_GENERIC, true>), g, b, 0, (hipStream_t)stream, x);
   HIP_TRY(e, hipGetLastError());
   return ARCLE_OK;
 }

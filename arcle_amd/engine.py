@@ -951,6 +951,39 @@ class EnvBatch:
                                              int(bool(through)), _ptr(region), _ptr(best), _ptr(bbits), _ptr(base), self._stream()), "arcle_region_rows")
         return out
 
+    def scale_rows(self, rows=None, src_env=None, sources=3, modes=7, out=None, table=False, bits=True):
+        """The grid or the input of every state row zoomed, shrunk or tiled onto the answer's canvas (arcle_scale_rows): rows, src_env
+        and sources as for `align_rows`; modes = the set of candidate families asked for (_lib.SCALE_ZOOM | SCALE_SHRINK |
+        SCALE_TILE).  Returns (scale int32 [M, 2, 8] = cand, correct, total, colours, sh, sw, ah, aw per source; table int32 [M, 2,
+        132] or None = correct of every candidate, -1 for a mode not asked for; bits uint8 [M, 2, 9, 128] or None = the best child's
+        cells of colour 1 .. 9 as bit rows; base int32 [M, 2] = the dense pair of the row's own grid): the candidate — index
+        (kx - 1) * 8 + (ky - 1): every cell a kx x ky block; 64 + the same: the top-left cell of every kx x ky block; 128 + t: the
+        source repeated, bit 0 / 1 of t mirroring every second tile column / row — whose child leaves the most correct cells, ties
+        to the lowest index; total = ah * aw, the child's dense total; cand -1 and total 0 where a dim is 0.  Slots of sources not
+        asked for are not written (zero in a fresh output).  The definition: include/arcle_scale_rows.h; its NumPy mirror:
+        arcle_amd.search.scale_numpy.  out: the four of a previous call with the same shapes (captured graphs).  Nothing of the
+        batch is touched."""
+        if rows is None:
+            M = int(out[0].shape[0]) if out is not None else int(src_env.shape[0]) if src_env is not None else self.N
+            ptr, stride = None, 0
+        else:
+            assert rows.dtype == torch.int8 and rows.dim() == 2 and rows.stride(1) == 1
+            M, ptr, stride = int(rows.shape[0]), _ptr(rows), rows.stride(0)
+        assert src_env is None or (src_env.dtype == torch.int32 and tuple(src_env.shape) == (M,) and src_env.is_contiguous())
+        if out is None:
+            out = (torch.zeros((M, 2, 8), dtype=torch.int32, device=self.device),
+                   torch.zeros((M, 2, _lib.SCALE_CANDS), dtype=torch.int32, device=self.device) if table else None,
+                   torch.zeros((M, 2, 9, _lib.BITS_STRIDE), dtype=torch.uint8, device=self.device) if bits else None,
+                   torch.zeros((M, 2), dtype=torch.int32, device=self.device))
+        scale, tab, cbits, base = out
+        assert scale.dtype == torch.int32 and tuple(scale.shape) == (M, 2, 8) and scale.is_contiguous()
+        assert tab is None or (tab.dtype == torch.int32 and tuple(tab.shape) == (M, 2, _lib.SCALE_CANDS) and tab.is_contiguous())
+        assert cbits is None or (cbits.dtype == torch.uint8 and tuple(cbits.shape) == (M, 2, 9, _lib.BITS_STRIDE) and cbits.is_contiguous())
+        assert base is None or (base.dtype == torch.int32 and tuple(base.shape) == (M, 2) and base.is_contiguous())
+        self._check(self.L.arcle_scale_rows(self._h, M, ptr, stride, _ptr(src_env), int(sources), int(modes), _ptr(scale), _ptr(tab), _ptr(cbits),
+                                            _ptr(base), self._stream()), "arcle_scale_rows")
+        return out
+
     def get_plane(self, name, out=None):
         """One key of the state dict as a dense [N, H, W] int8 array (device tensor, or a pinned host tensor passed as `out`):
         arcle_get_plane, a strided copy on the current stream."""

@@ -51,6 +51,21 @@ Rays = collections.namedtuple("Rays", "color correct cells right best_set best_c
 # what ARCVecEnv.regions returns: the same arrangement for the regions of arcle_region_rows (halo, box, frame, inside ...); best_kind is
 # the INDEX of the best candidate in the list of kinds asked for
 Regions = collections.namedtuple("Regions", "color correct cells right best_kind best_color best_correct best_cells best_bits base")
+# what ARCVecEnv.scale returns: views of one int32 [M, 2, 8] buffer (per source — the row's grid, the row's input — the best zoom, shrink
+# or tiling of the source onto the answer's canvas, its correct cells, the child's total, the colours of the child, the source's and the
+# answer's dims), cand decoded (kind 0 ZOOM, 1 SHRINK, 2 TILE, -1 none; kx, ky = the factors, for a TILE whether the tile rows / columns
+# are mirrored), the child's cells of colour 1 .. 9 as bit rows, the table of every candidate and the dense pair of every row's own grid
+Scales = collections.namedtuple("Scales", "cand correct total colours kind kx ky src_dim ans_dim bits table base")
+
+
+def scales_of(scale, table, bits, base):
+    """The outputs of `EnvBatch.scale_rows` (tensors of any device) as a Scales: cand decoded into kind, kx, ky"""
+    cand = scale[..., 0]
+    tile, none = cand >= 128, cand < 0
+    kind = torch.where(none, torch.full_like(cand, -1), torch.where(tile, torch.full_like(cand, 2), cand >> 6))
+    kx = torch.where(none, torch.zeros_like(cand), torch.where(tile, (cand >> 1) & 1, ((cand >> 3) & 7) + 1))
+    ky = torch.where(none, torch.zeros_like(cand), torch.where(tile, cand & 1, (cand & 7) + 1))
+    return Scales(cand, scale[..., 1], scale[..., 2], scale[..., 3], kind, kx, ky, scale[..., 4:6], scale[..., 6:8], bits, table, base)
 
 
 def _table_of(env_cls, **ctor_kw):
@@ -819,6 +834,22 @@ class ARCVecEnv:
             kinds.to(device=self.device, dtype=torch.uint8).contiguous()
         reg, best, bbits, base = self.batch.region_rows(rows, count, objs.bits.contiguous(), kinds, free_color, through, src_env, best_bits=bits)
         return Regions(reg[..., 0], reg[..., 1], reg[..., 2], reg[..., 3], best[..., 0], best[..., 1], best[..., 2], best[..., 3], bbits, base)
+
+    def scale(self, rows, src_env=None, sources=3, modes=7, table=False, bits=True):
+        """The grid or the input of every state row zoomed, shrunk or tiled onto the answer's canvas (arcle_scale_rows, one launch; no
+        step is run): rows, src_env and sources as for `align`; modes = the candidate families asked for (1 ZOOM: every cell a kx x ky
+        block, 2 SHRINK: the top-left cell of every kx x ky block, 4 TILE: the source repeated, plain or with every second tile column
+        / row mirrored; kx, ky in 1..8).  Returns a Scales of device tensors: cand, correct, total, colours [M, 2] = per source the
+        candidate whose child leaves the most correct cells (ties: the lowest index; -1: no candidate), that number, the child's
+        dense total ah * aw and the set of colours of the child (bit c); kind, kx, ky [M, 2] = cand decoded (kind 0 ZOOM, 1 SHRINK,
+        2 TILE, -1 none; for a TILE kx / ky = 1 where the tile rows / columns are mirrored); src_dim, ans_dim [M, 2, 2]; bits
+        [M, 2, 9, 128] = the child's cells of colour 1 .. 9 as bit rows (None with bits=False); table [M, 2, 132] = correct of every
+        candidate, -1 for a mode not asked for (None with table=False); base [M, 2] = the dense pair of the row's own grid.  Slots of
+        sources not asked for are zero.  `search.scale_macros` turns it into one [resize_grid, Color ...] macro per source.  This
+        env's state is not touched."""
+        if src_env is not None:
+            src_env = src_env.to(device=self.device, dtype=torch.int32).contiguous()
+        return scales_of(*self.batch.scale_rows(rows, src_env, sources, modes, table=table, bits=bits))
 
     def autotune(self, payload, operation=None, form="bbox"):
         """Times every launch plan the library has for this env's steps (self-ordering or not, the cache policies of the speculative grid

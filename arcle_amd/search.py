@@ -7,7 +7,9 @@ best translation of every object as ONE Move macro), and where a COPY of each ob
 arcle_stamp_rows; `stamp_macros` / `propose_stamps`: the best paste position of every object as ONE CopyO + Paste macro), and the
 lines each object casts toward the answer (`ray_numpy`: the host mirror of arcle_ray_rows; `ray_actions` / `propose_rays`: the best
 set of rays of every object as ONE Color step), and the cells around and inside each object (`region_numpy`: the host mirror of
-arcle_region_rows; `region_actions` / `propose_regions`: the best halo, box, frame or inside of every object as ONE Color step).
+arcle_region_rows; `region_actions` / `propose_regions`: the best halo, box, frame or inside of every object as ONE Color step), and the grid or the
+input zoomed, shrunk or tiled onto the answer's canvas (`scale_numpy`: the host mirror of arcle_scale_rows; `scale_macros` /
+`propose_scales`: the best candidate of every source as ONE resize_grid + Color macro).
 
 The hash is defined in include/arcle_hip.h (next to arcle_hash_rows) and computed on the device by arcle_amd/csrc/arcle_search.h;
 `hash_rows_numpy` restates it on the host — the same arrangement as arcle_amd/sampling.py for the device RNG — and is what the tests
@@ -1310,5 +1312,138 @@ def propose_regions(color_ops, kinds=None, free_color=0, through=False, box_ops=
             return ra
         single = object_actions(objs, box_ops, seed_ops, masks=True)
         return {"bits": torch.cat([single["bits"], ra["bits"]], 1).contiguous(), "operation": torch.cat([single["operation"], ra["operation"]], 1).contiguous()}
+    propose.wants_src = True
+    return propose
+
+
+# ---- the grid or the input zoomed, shrunk or tiled onto the answer's canvas ---------------------------------------------------------
+SCALE_ZOOM, SCALE_SHRINK, SCALE_TILE = 1, 2, 4  # ARCLE_SCALE_*: bit `mode` of `modes` <-> the candidates of that family
+SCALE_CANDS = 132
+
+
+def scale_candidates():
+    """The 132 candidates of arcle_scale_rows in index order -> list of (mode 0 ZOOM | 1 SHRINK | 2 TILE, kx, ky): the factors, for a
+    TILE whether the tile rows (kx) / the tile columns (ky) are mirrored in every second tile"""
+    return [(m, kx, ky) for m in (0, 1) for kx in range(1, 9) for ky in range(1, 9)] + [(2, t >> 1, t & 1) for t in range(4)]
+
+
+def _scale_map(mode, k, n_out, n_src):
+    """f (or g) of one candidate on 0 .. n_out - 1: the source index each takes its cell from, -1 where that lies outside [0, n_src)"""
+    t = np.arange(n_out)
+    if mode == 0:
+        s = t // k
+    elif mode == 1:
+        s = t * k
+    else:
+        q, r = t // n_src, t % n_src
+        s = np.where((q & 1) & k, n_src - 1 - r, r)
+    return np.where(s < n_src, s, -1)
+
+
+def scale_numpy(grid, grid_dim, inp, input_dim, answer, answer_dim, sources=3, modes=7, full=False):
+    """The best zoom, shrink or tiling of the grid and of the input of ONE state onto the answer's canvas as arcle_scale_rows reports it
+    (include/arcle_scale_rows.h) — the host mirror, straight from the definition: every child grid is built and counted.  grid, inp, answer
+    int8 [H, W]; sources = ALIGN_GRID | ALIGN_INPUT; modes = SCALE_ZOOM | SCALE_SHRINK | SCALE_TILE.  -> (scale int32 [2, 8] = cand,
+    correct, total, colours, sh, sw, ah, aw per source — slot 0 the grid, slot 1 the input; the slot of a source not asked for stays
+    zero —, base (correct, total) of the grid itself); full=True adds table int32 [2, 132]: correct of every candidate, -1 for a mode
+    not asked for (and everywhere in a slot without a candidate), and children int8 [2, 132, H, W]: the child grid of every candidate
+    on the whole plane.  The child of candidate (f, g): G'[i, j] = v(f(i), g(j)) on the canvas [0, ah) x [0, aw), v = the source's
+    bytes 1 .. 9 inside its dims, 0 for every other byte and index; ties go to the lowest index.  A dim of 0: cand -1, (0, 0, 0)."""
+    grid, inp, answer = (np.asarray(a).astype(np.int8) for a in (grid, inp, answer))
+    H, W = grid.shape
+    gh, gw = min(int(grid_dim[0]), H), min(int(grid_dim[1]), W)
+    ah, aw = min(int(answer_dim[0]), H), min(int(answer_dim[1]), W)
+    mh, mw = min(gh, ah), min(gw, aw)
+    total = mh * mw + (abs(ah * aw - gh * gw) if (gh <= ah) == (gw <= aw) else abs(gh - ah) * mw + abs(gw - aw) * mh)
+    base = (int((grid[:mh, :mw] == answer[:mh, :mw]).sum()), total)
+    scale = np.zeros((2, 8), np.int32)
+    table = np.full((2, SCALE_CANDS), -1, np.int32)
+    children = np.zeros((2, SCALE_CANDS, H, W), np.int8)
+    for s, (src, dim) in enumerate(((grid, grid_dim), (inp, input_dim))):
+        if not (int(sources) >> s) & 1:
+            continue
+        sh, sw = max(min(int(dim[0]), H), 0), max(min(int(dim[1]), W), 0)
+        scale[s] = (-1, 0, 0, 0, sh, sw, ah, aw)
+        if min(sh, sw, ah, aw) < 1:
+            continue
+        v = np.zeros((sh + 1, sw + 1), np.int8)  # (row / column -1: the zero every index outside the source reads)
+        v[:sh, :sw] = np.where((src[:sh, :sw] >= 1) & (src[:sh, :sw] <= 9), src[:sh, :sw], 0)
+        best = None
+        for c, (mode, kx, ky) in enumerate(scale_candidates()):
+            if not (int(modes) >> mode) & 1:
+                continue
+            child = v[_scale_map(mode, kx, ah, sh)][:, _scale_map(mode, ky, aw, sw)]
+            children[s, c, :ah, :aw] = child
+            table[s, c] = int((child == answer[:ah, :aw]).sum())
+            if best is None or table[s, c] > table[s, best]:
+                best = c
+        colours = sum(1 << int(k) for k in np.unique(children[s, best]) if k)
+        scale[s, :4] = (best, table[s, best], ah * aw, colours)
+    return (scale, base, table, children) if full else (scale, base)
+
+
+def scale_macros(scales, resize_op, color_ops, H, W):
+    """The best candidate of every source (`ARCVecEnv.scale` -> Scales, with its bit rows) as ONE macro per source: {"bits": uint8
+    [M, 2, 10, 128], "operation": int32 [M, 2, 10], "length": int32 [M, 2]}.  Step 0 is the canvas rectangle (0, 0)..(ah - 1, aw - 1)
+    with resize_op (resize_grid), then `Color c` — color_ops[c], c = 0..9 — on the child's cells of colour c for every colour present,
+    ascending, packed to the front: length = 1 + popcount(colours); the steps behind it have operation -1 and zero bit rows.  A slot
+    with total == 0 (not asked for, or no candidate) or that does not beat the row's own ratio by `align_macros`' rule — correct *
+    base_total <= base_correct * total, in integers — gets operation -1 at every step and length 1: one ARCLE_ST_BAD_OP child, dropped
+    by beam_search.  Built on the device by sorting and indexing: no host synchronisation."""
+    a = scales
+    assert a.bits is not None, "scale_macros needs the child's bit rows (scale(bits=True))"
+    dev = a.cand.device
+    M = int(a.cand.shape[0])
+    ops = torch.as_tensor([int(o) for o in color_ops], dtype=torch.int32, device=dev)
+    assert int(ops.numel()) == 10, "color_ops: the ten Color ops, color_ops[c] paints c"
+    ah, aw = a.ans_dim[..., 0].to(torch.int64), a.ans_dim[..., 1].to(torch.int64)
+    zero = torch.zeros_like(ah)
+    bc, bt = a.base[:, 0].to(torch.int64).reshape(M, 1), a.base[:, 1].to(torch.int64).reshape(M, 1)
+    ok = (a.total > 0) & (a.correct.to(torch.int64) * bt > bc * a.total.to(torch.int64))
+    c = torch.arange(1, 10, device=dev, dtype=torch.int64).reshape(1, 1, 9)
+    present = ((a.colours.to(torch.int64).reshape(M, 2, 1) >> c) & 1) != 0
+    order = torch.argsort(torch.where(present, c, c + 16), dim=2)  # (the colours present first, ascending)
+    n = present.sum(2)
+    live = (torch.arange(9, device=dev).reshape(1, 1, 9) < n.reshape(M, 2, 1)) & ok.reshape(M, 2, 1)
+    cbits = torch.gather(a.bits, 2, order.reshape(M, 2, 9, 1).expand(M, 2, 9, int(a.bits.shape[-1])))
+    none8, none32 = torch.zeros((), dtype=torch.uint8, device=dev), torch.full((), -1, dtype=torch.int32, device=dev)
+    cbits = torch.where(live.reshape(M, 2, 9, 1), cbits, none8)
+    cops = torch.where(live, ops[order + 1], none32)
+    rbits = torch.where(ok.reshape(M, 2, 1), _rect_bits(zero, ah - 1, zero, aw - 1, H, W), none8)
+    rop = torch.where(ok, torch.full((), int(resize_op), dtype=torch.int32, device=dev), none32)
+    length = torch.where(ok, (1 + n).to(torch.int32), torch.ones((), dtype=torch.int32, device=dev))
+    return {"bits": torch.cat([rbits.reshape(M, 2, 1, -1), cbits], 2).contiguous(),
+            "operation": torch.cat([rop.reshape(M, 2, 1), cops], 2).to(torch.int32).contiguous(), "length": length.to(torch.int32).contiguous()}
+
+
+def propose_scales(resize_op, color_ops, sources=3, modes=7, box_ops=(), seed_ops=(), max_components=16, skip_color=0, any_color=False,
+                   diagonal=False):
+    """A `propose` for beam_search that answers "is the answer the grid, or the input, zoomed, shrunk or tiled?" — like
+    `propose_alignments` its children have the answer's grid_dim: at every depth, for each frontier state, ONE macro per source asked
+    for — resize_op (resize_grid) to the answer's dims, then one `Color c` per colour of the best candidate's child on that colour's
+    cells (`venv.scale`, one launch; `scale_macros`): K = 2, T = 10.  color_ops[c] = the index of `Color c` in the env's op table
+    (both default tables: range(10)).  With box_ops / seed_ops the singles of `object_actions(masks=True)` on the objects of each
+    state's grid come first, as macros of length 1, the way `propose_alignments` puts them: K = C * (len(box_ops) + len(seed_ops)) +
+    2.  It looks at the answer of each row's env, so it carries `wants_src = True` and beam_search calls it with (venv, rows, src_env)."""
+    resize_op, color_ops = int(resize_op), [int(o) for o in color_ops]
+    box_ops, seed_ops = list(box_ops), list(seed_ops)
+
+    def propose(venv, rows, src_env=None):
+        sm = scale_macros(venv.scale(rows, src_env, sources, modes), resize_op, color_ops, venv.H, venv.W)
+        if not box_ops and not seed_ops:
+            return sm
+        if any_color or diagonal:
+            objs = venv.objects(rows, max_components=max_components, skip_color=skip_color, any_color=any_color, diagonal=diagonal, bits=True)
+        else:
+            objs = venv.components(rows, max_components=max_components, skip_color=skip_color, bits=True)
+        single = object_actions(objs, box_ops, seed_ops, masks=True)
+        M, K1 = (int(v) for v in single["operation"].shape)
+        dev = single["bits"].device
+        b1 = torch.zeros((M, K1, 10, int(single["bits"].shape[-1])), dtype=torch.uint8, device=dev)
+        b1[:, :, 0] = single["bits"]
+        o1 = torch.full((M, K1, 10), -1, dtype=torch.int32, device=dev)
+        o1[:, :, 0] = single["operation"]
+        return {"bits": torch.cat([b1, sm["bits"]], 1).contiguous(), "operation": torch.cat([o1, sm["operation"]], 1).contiguous(),
+                "length": torch.cat([torch.ones((M, K1), dtype=torch.int32, device=dev), sm["length"]], 1).contiguous()}
     propose.wants_src = True
     return propose

@@ -654,7 +654,8 @@ int arcle_turn_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t 
  * goal exactly when correct == total.  The best offset maximises correct; ties go to the smaller |ox| + |oy|, then the smaller ox,
  * then the smaller oy (arcle_place_rows' rule).  base is the dense pair of the row's own grid, as the siblings write it.  A row whose
  * src_env names no env gets base = (0, 0) and all-zero slots.
- * A one-step crop_grid form, turned or scaled sources and the objects of the input are out of scope.
+ * A one-step crop_grid form, turned sources and the objects of the input are out of scope (zoomed, shrunk and tiled sources:
+ * arcle_scale_rows).
  * No side effects; allocates nothing: may be captured.  One wavefront per row.  Refusals, nothing written: n_rows <= 0, a stride below
  * the row length, align NULL, max_dist < 0, sources == 0 or a bit above ARCLE_ALIGN_INPUT, blank outside {0, 1}, rows == NULL with
  * n_rows > n_envs (with or without src_env: row m's grid is env m's): ARCLE_ERR_ARG; more than ARCLE_MAX_CELLS cells per plane, or an
@@ -811,6 +812,10 @@ int arcle_mirror_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_
 int arcle_region_rows(arcle_env* env, int32_t n_rows, const int8_t* rows, int32_t stride, int32_t max_comp, const int32_t* count,
                       const uint8_t* bits, const int32_t* src_env, const uint8_t* kinds, int32_t n_kinds, int32_t free_color,
                       int32_t through, int32_t* region, int32_t* best, uint8_t* best_bits, int32_t* base, void* stream);
+/* The grid or the input of a state row zoomed, shrunk or tiled onto the answer's canvas: an EXTENSION of ABI 18, declared in a header of
+ * its own.  ARCLE_ABI_VERSION and the entry points declared in this file stay as they are; a library that carries the extension defines
+ * ARCLE_HAS_SCALE_ROWS there and exports its one entry point beside these. */
+#include "arcle_scale_rows.h"
 /* One state plane as a dense [n_envs][H*W] int8 array (device or pinned host memory), a strided copy on the stream: the
  * get_state()/set_state() of single keys of the reference's state dict. */
 int arcle_get_plane(arcle_env* env, int plane, int8_t* dst, void* stream);
